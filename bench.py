@@ -6,6 +6,11 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
     python bench.py --gpus 2 --oversubscribe       # TEST ONLY: N ranks share the visible GPU(s) (gloo group), exercises the N > 1 path
+    python bench.py --gpus 1 --full                # + GPU clocks, 3 timed regions, CPU baseline, PPO lines, the other workloads
+    python bench.py --gpus 1 --dump-outputs DIR    # + what the last timed step returned, as DIR/<name>.npy
+
+A plain run sets up, warms up, times exactly --steps steps and prints the result line; everything else it can measure is
+behind --full.
 
 One "step" = one env.step over the whole per-GPU batch, as ONE kernel launch (mm_rollout_step): draw actions U[0,1) on the
 device (benchmarks/mjx_benchmark.py:29), muscle ctrl map, frame_skip physics substeps, the post-step mj_forward, obs /
@@ -35,6 +40,8 @@ PMC_PROFILE = os.path.join(ROOT, "profiles", "r06d_pmc.json")
 ACCURACY_PROFILE = os.path.join(ROOT, "profiles", "r06_accuracy.json")     # tests/tools/gpu_accuracy_run.py (replayed into the line)
 REPEATS = 3                 # timed regions of --steps steps each; the line reports the median region
 EXTRA_MIN_TIMED_MS = 60.0   # an extra line times at least this much kernel work (a 1.5 ms timed region is launch-noise bound)
+FULL_EXTRAS_FILE = os.path.join(ROOT, "runs", "bench_extras.json")    # --full's default --extras-file (runs/ is ignored)
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: above this, a fixed seeded sample of env rows is written (and its indices)
 # Order matters: the driver's record keeps the TAIL of the printed line, so the BASELINE.json configs 2 / 4 / 5 (elbow, reorient,
 # fati-leg) come last, and a compact `baseline_configs` digest of every line closes the JSON.
 EXTRA_CONFIGS = [# the step of the reference's own GPU path: mjx_env.step = n_substeps x mjx.step, observation straight from the
@@ -284,7 +291,7 @@ def measure(env_id, n, steps, warmup, rank, world, lanes=0, seed=0, overrides=No
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for s in range(steps):
-            env.rollout_step(None, stream_id=warmup + r * steps + s, events=evs[s])   # events bracket the fused env-step kernel alone
+            last = env.rollout_step(None, stream_id=warmup + r * steps + s, events=evs[s])   # events bracket the fused env-step kernel alone
         stats = D.gather_episode_stats(ep_stats)   # the one collective of a rollout
         torch.cuda.synchronize()
         D.barrier()
@@ -294,6 +301,7 @@ def measure(env_id, n, steps, warmup, rank, world, lanes=0, seed=0, overrides=No
     order = sorted(range(repeats), key=lambda i: regions[i][0])
     med = regions[order[(repeats - 1) // 2]]          # the median region (lower median for an even count)
     measure.ep_stats = ep_stats
+    measure.last_outputs = last                       # (obs, reward rows, reset mask) of the last timed step: views the next step rewrites
     measure.own_elapsed_of_median_region = med[2]     # this rank's own clock around the region `value` is quoted on (N > 1 line: per-rank values)
     return med[0], med[1], env, stats, [e for e, _, _ in regions]
 
@@ -333,6 +341,24 @@ def collective_report(ep_stats, stats, n, world, own_elapsed, steps):
             "what": "one all-gather of [E, 3] episode statistics per rollout; no collective on the step path",
             "gathered_rows": int(stats.shape[0]), "expected_rows": world * n, "bytes_per_rank": int(ep_stats.numel() * ep_stats.element_size()),
             "allgather_us": 1e6 * ts[len(ts) // 2], "per_rank_env_steps_per_s": [float(p.item()) for p in parts]}
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: `arrays` (name -> device tensor with one row per env) as out_dir/<name>.npy, fp64 kept and everything else
+    cast to fp32.  Above DUMP_LIMIT_BYTES in all, the same fixed seeded sample of env rows is taken from every array and its row
+    indices are written as env_rows.npy."""
+    import numpy as np
+    host = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    host = {k: v if v.dtype == np.float64 else v.astype(np.float32) for k, v in host.items()}
+    n = len(next(iter(host.values())))
+    row_bytes = sum(v.nbytes for v in host.values()) / max(1, n)
+    if row_bytes * n > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, int(DUMP_LIMIT_BYTES // (row_bytes + 8)), replace=False))
+        host = {k: v[rows] for k, v in host.items()}
+        host["env_rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 def roofline(env, env_id, n, kern_ms, overrides=None):
@@ -534,15 +560,24 @@ def main():
     ap.add_argument("--config", type=int, default=0, choices=[0, 2, 3, 4, 5],
                     help="preset = BASELINE.json config number: 2 elbow@4096, 3 hand@4096 (the default headline), 4 reorient@2048, "
                          "5 myoFatiLegWalk-v0@1024 per GPU (8192 over 8: `--gpus 8 --config 5`); overrides --env / --envs-per-gpu")
-    ap.add_argument("--repeats", type=int, default=REPEATS, help="timed regions of --steps steps each (median reported)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-ppo", action="store_true", help="skip the ppo_training lines (whole PPO iterations on the device)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra_configs lines (elbow / reorient / leg-walk / self-contact hand)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help=f"timed regions of --steps steps each (median reported); default 1, {REPEATS} with --full")
+    ap.add_argument("--full", action="store_true",
+                    help="also log the GPU clocks, time the CPU baseline, the ppo_training lines and the extra_configs lines, and "
+                         "write the extras file: what a plain run leaves out to keep to its headline figure")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one returned (observations, reward rows, reset mask, episode "
+                         "statistics; rank 0's envs) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline block")
+    ap.add_argument("--no-ppo", action="store_true", help="with --full: skip the ppo_training lines (whole PPO iterations on the device)")
+    ap.add_argument("--no-extra", action="store_true",
+                    help="with --full: skip the extra_configs lines (elbow / reorient / leg-walk / self-contact hand)")
     ap.add_argument("--model", default=None, help="model override of the headline env (e.g. hand_contact): profile collection")
     ap.add_argument("--no-forward", action="store_true", help="do_forward=False override of the headline env: profile collection")
     ap.add_argument("--precision", default=None, help="precision override of the headline env (f64 | f64_state): profile collection")
-    ap.add_argument("--extras-file", default=os.path.join(ROOT, "gpurun_out", "bench_extras.json"),
-                    help="everything beyond the compact contract line (extra_configs, ppo_training, replayed counters, launch geometry)")
+    ap.add_argument("--extras-file", default=None,
+                    help="everything beyond the compact contract line (extra_configs, ppo_training, replayed counters, launch geometry); "
+                         f"default with --full: {os.path.relpath(FULL_EXTRAS_FILE, ROOT)}, none otherwise")
     ap.add_argument("--oversubscribe", action="store_true",
                     help="TEST ONLY: rank r runs on cuda:(r %% visible devices) and the process group is gloo, so that the N > 1 code "
                          "path (launcher respawn, barrier, max over ranks, stats gather, sharded Philox streams) can be exercised on a "
@@ -550,6 +585,12 @@ def main():
     args = ap.parse_args()
     if args.config:
         args.env, args.envs_per_gpu = BASELINE_PRESETS[args.config]
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.repeats is None:
+        args.repeats = REPEATS if args.full else 1
+    if args.extras_file is None and args.full:
+        args.extras_file = FULL_EXTRAS_FILE
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(respawn_under_launcher(args))
@@ -576,10 +617,13 @@ def main():
         head_ov["do_forward"] = False
     if args.precision:
         head_ov["precision"] = args.precision
-    clocks_before = gpu_clocks() if rank == 0 else None
+    clocks_before = gpu_clocks() if rank == 0 and args.full else None
     elapsed, kern_ms, env, stats, regions = measure(args.env, n, args.steps, args.warmup, rank, world, args.lanes, overrides=head_ov,
                                                     repeats=max(1, args.repeats))
-    clocks_after = gpu_clocks() if rank == 0 else None
+    clocks_after = gpu_clocks() if rank == 0 and args.full else None
+    if args.dump_outputs and rank == 0:
+        obs, rwd, reset_mask = measure.last_outputs
+        dump_outputs(args.dump_outputs, {"obs": obs, "reward_rows": rwd, "reset_mask": reset_mask, "episode_stats": measure.ep_stats})
     cm = env.cm
     # every rank takes part (one small all-gather + the per-rank values); only rank 0 prints
     coll = collective_report(measure.ep_stats, stats, n, world, measure.own_elapsed_of_median_region, args.steps) if world > 1 else None
@@ -593,7 +637,6 @@ def main():
             "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": 1e3 * elapsed / args.steps, "repeats": len(regions),
             "region_ms_per_step": [1e3 * e / args.steps for e in regions],      # every timed region; `value` is the median one
-            "gpu_clocks_mhz": {"before": clocks_before, "after": clocks_after},
             "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": prec_name[int(getattr(env, "precision", 0))], "data": "synthetic",
             "config": {"workload": f"{args.env}, {n} envs/GPU, random actions, one fused launch per env-step (synthetic model {cm.name})",
@@ -606,6 +649,8 @@ def main():
             "stats": {"mean_episode_return": float(stats[:, 0].mean()), "solved_frac": float(stats[:, 2].mean()),
                       "envs_in_stats": int(stats.shape[0]), "status_or": status_or(env.state.status)},
         }
+        if args.full:
+            out["gpu_clocks_mhz"] = {"before": clocks_before, "after": clocks_after}
         if coll is not None:
             out["collective"] = coll
         if args.config:
@@ -618,15 +663,15 @@ def main():
             "env_steps_per_s": value, "kernel_ms": kern_ms, "hbm_frac_8d": out["roofline"]["frac"],
             "fp32_peak_frac": (out["roofline"].get("flops") or {}).get("frac"), "traffic_over_algorithmic": out["roofline"]["traffic_over_algorithmic"]}}
         del env
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # ~12 s of wall time on rank 0's host cores, after the timed region (the other ranks wait in destroy_process_group)
             out["cpu_baseline"] = cpu_baseline(args.env)
-        if world == 1 and not args.no_extra and not args.no_ppo:
+        if args.full and world == 1 and not args.no_extra and not args.no_ppo:
             out["ppo_training"] = ppo_training_lines()
         for line in out.get("ppo_training", []):
             digest[line["key"]] = ({"train_env_steps_per_s": line["train_env_steps_per_s"], "rollout_env_steps_per_s": line["rollout_env_steps_per_s"]}
                                    if "error" not in line else {"error": line["error"][:120]})
-        if world == 1 and not args.no_extra:
+        if args.full and world == 1 and not args.no_extra:
             # driver-visible numbers for the other BASELINE.json configs (same timed loop, shorter): not the headline value
             extra = []
             for env_id, ne, ov in EXTRA_CONFIGS:

@@ -106,7 +106,7 @@ def test_bench_n_gt_1_path_runs_oversubscribed_on_one_gpu():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--oversubscribe", "--steps", str(K), "--warmup", str(W),
-                          "--envs-per-gpu", str(E_), "--no-extra", "--repeats", "1"], env=env, capture_output=True, text=True, timeout=900)
+                          "--envs-per-gpu", str(E_), "--full", "--no-extra", "--repeats", "1"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout
@@ -170,13 +170,13 @@ def _fracs(node, path=""):
 
 @pytest.mark.gpu
 def test_bench_line_bookkeeping_repeats_fractions_and_replayed_counters(tmp_path):
-    """The default run (short): the LAST stdout line is the compact contract line (< 4 KB: the round-5 line had grown to 27 KB and the
+    """The --full run (short): the LAST stdout line is the compact contract line (< 4 KB: the round-5 line had grown to 27 KB and the
     driver could not read it back), everything else is in the extras file.  `repeats` timed regions with the median reported, no fraction above 1 anywhere (the valu-busy
     fraction is priced per RESIDENT wave: mm_model_launch_info), counters that were not measured in the run sit under
     roofline.profile and name the committed file they are replayed from, the GPU clocks are logged around the timed region."""
     import subprocess, sys
     xf = str(tmp_path / "bench_extras.json")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--warmup", "2", "--extras-file", xf],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--warmup", "2", "--full", "--extras-file", xf],
                          capture_output=True, text=True, timeout=1500)
     assert out.returncode == 0, out.stderr[-2000:]
     last = out.stdout.rstrip().splitlines()[-1]
@@ -222,3 +222,63 @@ def test_bench_line_bookkeeping_repeats_fractions_and_replayed_counters(tmp_path
     assert hand["rollout_env_steps_per_s"] >= hand["train_env_steps_per_s"]
     prec = [x for x in d["extra_configs"] if x["key"] == "myoHandPoseRandom-v0@4096|precision=f64_state"][0]
     assert prec["dtype"] == "f64" and prec["value"] >= 1.0e6          # BASELINE.json's throughput target holds in precision mode too
+
+
+def test_dump_outputs_keeps_fp64_casts_the_rest_to_fp32_and_samples_rows_above_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: one <name>.npy per array, fp64 kept and everything else fp32; above DUMP_LIMIT_BYTES the same fixed seeded
+    env rows of every array (and their indices, env_rows.npy), identical from call to call and within the limit."""
+    import importlib.util
+    import numpy as np
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    arrays = {"obs": torch.arange(400, dtype=torch.float32).reshape(100, 4), "reset_mask": (torch.arange(100) % 3 == 0).to(torch.uint8),
+              "episode_stats": torch.linspace(-1, 1, 300, dtype=torch.float64).reshape(100, 3)}
+    b.dump_outputs(str(tmp_path / "all"), arrays)
+    got = {k: np.load(tmp_path / "all" / f"{k}.npy") for k in arrays}
+    assert sorted(os.listdir(tmp_path / "all")) == sorted(f"{k}.npy" for k in arrays)
+    assert got["obs"].dtype == np.float32 and got["reset_mask"].dtype == np.float32 and got["episode_stats"].dtype == np.float64
+    for k, v in arrays.items():
+        np.testing.assert_array_equal(got[k], v.numpy())
+    monkeypatch.setattr(b, "DUMP_LIMIT_BYTES", 1000)
+    for d in ("s1", "s2"):
+        b.dump_outputs(str(tmp_path / d), arrays)
+    rows = np.load(tmp_path / "s1" / "env_rows.npy")
+    assert 0 < len(rows) < 100 and np.all(np.diff(rows) > 0)
+    assert sum(os.path.getsize(tmp_path / "s1" / f) - 128 for f in os.listdir(tmp_path / "s1")) <= 1000      # (128 B .npy header)
+    for k, v in arrays.items():
+        s1, s2 = np.load(tmp_path / "s1" / f"{k}.npy"), np.load(tmp_path / "s2" / f"{k}.npy")
+        np.testing.assert_array_equal(s1, s2)
+        np.testing.assert_array_equal(s1, v.numpy()[rows.astype(int)].astype(s1.dtype))
+
+
+@pytest.mark.gpu
+def test_plain_run_times_exactly_steps_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) times ONE region of exactly --steps steps and measures nothing else (no CPU baseline, PPO or extra
+    lines, clocks, extras file); --dump-outputs writes what the last timed step returned, the same arrays for two runs with the
+    same arguments."""
+    import subprocess, sys
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        dump = tmp_path / f"dump{k}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+                              "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = out.stdout.rstrip().splitlines()
+        assert [l for l in lines if l.startswith("{")] == [lines[-1]]
+        c = json.loads(lines[-1])
+        _check_compact_line(c, cpu=False)
+        assert c["steps"] == 5 and c["warmup"] == 2 and c["extras"] is None and "cpu_baseline" not in c and c["dtype"] == "f32"
+        full = json.loads([l for l in lines if l.startswith("#extra ")][-1][len("#extra "):])
+        assert full["repeats"] == 1 and len(full["region_ms_per_step"]) == 1 and full["region_ms_per_step"][0] == pytest.approx(c["ms_per_step"])
+        for k_ in ("cpu_baseline", "ppo_training", "extra_configs", "gpu_clocks_mhz"):
+            assert k_ not in full, k_
+        assert list(c["baseline_configs"]) == ["myoHandPoseRandom-v0@4096 [headline]"]
+        dumps.append({f[:-4]: np.load(dump / f) for f in os.listdir(dump)})
+    assert sorted(dumps[0]) == ["episode_stats", "obs", "reset_mask", "reward_rows"]
+    assert dumps[0]["obs"].shape[0] == 4096 and dumps[0]["obs"].ndim == 2 and dumps[0]["episode_stats"].shape == (4096, 3)
+    for k, v in dumps[0].items():
+        assert v.dtype == np.float32 and np.all(np.isfinite(v)), k
+        np.testing.assert_array_equal(v, dumps[1][k], err_msg=k)

@@ -9,6 +9,10 @@ from myosuite_amd.model import mjcf, synth
 from oracle import oracle as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# the reference's task XMLs (myosuite/envs/myo/assets, stored with their relative layout so that their includes still point into
+# the empty simhive/myo_sim submodule)
+REF_ROOT = os.path.join(ROOT, "tests", "golden", "reference_assets")
+REF_ASSETS = os.path.join(REF_ROOT, "myosuite", "envs", "myo", "assets")
 
 
 @pytest.mark.parametrize("name", ["elbow", "hand", "leg", "contact_toy", "hand_reorient", "friction_toy", "hand_keyturn", "finger",
@@ -120,9 +124,7 @@ def test_include_and_unsupported_features_fail_loudly(tmp_path):
 def test_reference_task_xml_parses_up_to_the_missing_submodule():
     """The reference's task XMLs only <include> the empty myo_sim submodule: with missing includes skipped, what is in-repo
     (object / target bodies of myohand_sar.xml) imports; convex / mesh content would raise instead of being dropped."""
-    path = "/root/reference/myosuite/envs/myo/assets/hand/myohand_sar.xml"
-    if not os.path.exists(path):
-        pytest.skip("reference checkout not present (GPU box)")
+    path = os.path.join(REF_ASSETS, "hand", "myohand_sar.xml")
     s = mjcf.load(path, missing_include="skip")
     assert [s.joints[j].name for j in s.bodies[s._bname["Object"]].joints] == ["OBJTx", "OBJTy", "OBJTz", "OBJRx", "OBJRy", "OBJRz"]
     obj = s.geoms[s._gname["obj"]]
@@ -225,13 +227,11 @@ def test_task_xml_resolves_against_a_standin_myo_sim_tree(oracle_lib, tmp_path):
         d.step(30)
     assert np.abs(d0.qpos - d1.qpos).max() < 1e-12
     np.testing.assert_allclose(d1.ten_length[:base.ntendon], d0.ten_length, atol=1e-14)
-    # the reference's own task file resolves against the same tree (where the reference checkout exists)
-    ref = "/root/reference/myosuite/envs/myo/assets/hand/myohand_pose.xml"
-    if os.path.exists(ref):
-        s_ref = mjcf.load(ref, include_map=imap)
-        cm_ref = s_ref.compile()
-        assert np.array_equal(cm_ref.blob, cm.blob)                      # same model: the task file adds exactly what ours adds
-        assert len(s_ref.keys) == 1 and len(s_ref.keys[0][0]) == 23      # its keyframe (xml:24-26)
+    # the reference's own task file resolves against the same tree
+    s_ref = mjcf.load(os.path.join(REF_ASSETS, "hand", "myohand_pose.xml"), include_map=imap)
+    cm_ref = s_ref.compile()
+    assert np.array_equal(cm_ref.blob, cm.blob)                      # same model: the task file adds exactly what ours adds
+    assert len(s_ref.keys) == 1 and len(s_ref.keys[0][0]) == 23      # its keyframe (xml:24-26)
     # a missing tree still fails loudly
     with pytest.raises(mjcf.MjcfError):
         mjcf.load(path, include_map={"simhive/myo_sim": str(tmp_path / "nowhere")})
@@ -316,12 +316,10 @@ def test_dry_run_lists_every_construct_the_importer_would_reject():
     ok = mjcf.dump(synth.make_hand())
     r2 = mjcf.dry_run(ok)
     assert r2["loadable"] and not r2["unsupported"] and not r2["missing_includes"]
-    ref = "/root/reference/myosuite/envs/myo/assets"
-    if os.path.isdir(ref):
-        sar = mjcf.dry_run(os.path.join(ref, "hand", "myohand_sar.xml"))
-        assert len(sar["missing_includes"]) == 3 and all("simhive/myo_sim" in f for f in sar["missing_includes"]) and not sar["unsupported"]
-        leg = mjcf.dry_run(os.path.join(ref, "leg", "myolegs_chasetag.xml"))
-        assert any(k.startswith("hfield geom") for k in leg["unsupported"]) and len(leg["missing_includes"]) == 7
+    sar = mjcf.dry_run(os.path.join(REF_ASSETS, "hand", "myohand_sar.xml"))
+    assert len(sar["missing_includes"]) == 3 and all("simhive/myo_sim" in f for f in sar["missing_includes"]) and not sar["unsupported"]
+    leg = mjcf.dry_run(os.path.join(REF_ASSETS, "leg", "myolegs_chasetag.xml"))
+    assert any(k.startswith("hfield geom") for k in leg["unsupported"]) and len(leg["missing_includes"]) == 7
 
 
 MYO_SIM_STYLE = """<mujoco model="myo_like">
@@ -394,7 +392,7 @@ def test_committed_mjcf_inventory_of_the_reference_task_files():
     """profiles/r05_mjcf_dry_run.json (tools/mjcf_inventory.py over <reference>/myosuite/envs/myo/assets): the importer's only
     rejections are the documented physics gaps -- mesh / height-field COLLISION geoms, inertia from meshes, rolling friction (condim 6: two
     MyoChallenge files) -- plus one file
-    that is an include fragment, not a model.  Re-derived and compared when the reference checkout is present."""
+    that is an include fragment, not a model.  Re-derived from the task XMLs stored under tests/golden/reference_assets and compared."""
     import json
     import subprocess
     import sys
@@ -405,7 +403,7 @@ def test_committed_mjcf_inventory_of_the_reference_task_files():
                 or "root element must be <mujoco>" in why), (f, why)
     for kind in inv["unsupported_constructs_by_number_of_files"]:
         assert kind.startswith(("mesh geom that collides", "hfield geom that collides", "colliding geom with condim 6")), kind
-    if os.path.isdir("/root/reference/myosuite/envs/myo/assets"):
-        now = json.loads(subprocess.check_output([sys.executable, os.path.join(ROOT, "tools", "mjcf_inventory.py")], text=True))
-        assert now["importer_rejections_with_includes_skipped"] == inv["importer_rejections_with_includes_skipped"]
-        assert now["unsupported_constructs_by_number_of_files"] == inv["unsupported_constructs_by_number_of_files"]
+    now = json.loads(subprocess.check_output([sys.executable, os.path.join(ROOT, "tools", "mjcf_inventory.py"), REF_ROOT], text=True))
+    assert now["files_total"] == inv["files_total"]
+    assert now["importer_rejections_with_includes_skipped"] == inv["importer_rejections_with_includes_skipped"]
+    assert now["unsupported_constructs_by_number_of_files"] == inv["unsupported_constructs_by_number_of_files"]
