@@ -367,7 +367,15 @@ extern "C" int mm_model_create(const uint32_t* blob, int nwords, mm_model** out)
     const float* fl = (const float*)(blob + m->sec[MM_SEC_DOF_FRICTIONLOSS]);
     for (int i = 0; i < d.nv; i++) if (fl[i] > 0.f) d.nfric++;
   }
-  d.gen = (d.neq > 0 || d.npair > 0 || d.nfric > 0 || d.ntlim > 0) ? 1 : 0;
+  int nlimjnt = 0;     // limited hinge / slide joints: the limit-rows-only kernel makes one row for each, it never reads njmax
+  {
+    const int32_t* jt = (const int32_t*)(blob + m->sec[MM_SEC_JNT_TYPE]);
+    const int32_t* jl = (const int32_t*)(blob + m->sec[MM_SEC_JNT_LIMITED]);
+    for (int j = 0; j < d.njnt; j++) if (jl[j] && (jt[j] == MM_JNT_HINGE || jt[j] == MM_JNT_SLIDE)) nlimjnt++;
+  }
+  // (an explicit njmax below the limit count takes the general-row kernel, which drops the rows beyond it as the oracle does; the
+  // derived njmax counts every limit, so no shipped model changes family)
+  d.gen = (d.neq > 0 || d.npair > 0 || d.nfric > 0 || d.ntlim > 0 || d.njmax < nlimjnt) ? 1 : 0;
   {
     // dof-tree depth.  The limit-rows-only kernels keep M tree-sparse with at most 8 entries per row (dof + 7 ancestors);
     // a deeper tree takes the general-row kernels, whose factorisations are dense.

@@ -2712,8 +2712,12 @@ struct Engine {
     }
     GSYNC();
     const int neq = KD().neq;
+    // the row bound of every row kind is the model's njmax, as in the oracle's add_row (efc_rows, the table size, rounds it up to 4)
+    const int rmax = KD().njmax < KD().efc_rows ? KD().njmax : KD().efc_rows;
+    int over = 0;
     // ---- equality rows: joint coupling q1 - q1_0 = poly(q2 - q2_0)
-    if (g < neq) {
+    if (g < neq && g >= rmax) over = 1;
+    else if (g < neq) {
       const int e = g, j1 = MI_(EQ_OBJ1ID)[e], j2 = MI_(EQ_OBJ2ID)[e];
       const float* c = MF_(EQ_DATA) + 5 * e;
       const int q1 = MI_(JNT_QPOSADR)[j1], d1 = MI_(JNT_DOFADR)[j1];
@@ -2738,10 +2742,10 @@ struct Engine {
       nfr = gsum_i(fr);
       if (fr) {
         const int r = neq + frank;
-        if (r < KD().efc_rows) {
+        if (r < rmax) {
           Jrow(r)[g] = 1.f;
           RT[3 * r] = __int_as_float(MM_CON_FRICTION_DOF | (g << 3)); RT[3 * r + 1] = 0.f; RT[3 * r + 2] = MF_(DOF_INVWEIGHT0)[g];
-        }
+        } else over = 1;
       }
     }
     // ---- joint limits, compacted behind the equalities
@@ -2762,10 +2766,9 @@ struct Engine {
       }
     }
     const int lrank = gscan_flag(lim != 0), nlim = gsum_i(lim);
-    int over = 0;
     if (lim) {
       const int r = neq + nfr + lrank;
-      if (r < KD().efc_rows) {
+      if (r < rmax) {
         Jrow(r)[ldof] = lsign;
         RT[3 * r] = __int_as_float(MM_CON_LIMIT_JOINT | (g << 3)); RT[3 * r + 1] = ldist - lmargin; RT[3 * r + 2] = MF_(DOF_INVWEIGHT0)[ldof];
       } else over = 1;
@@ -2788,7 +2791,7 @@ struct Engine {
         const int trank = gscan_flag(tl != 0), tcnt = gsum_i(tl);
         if (tl) {
           const int r = neq + nfr + nlim + ntl + trank;
-          if (r < KD().efc_rows) {
+          if (r < rmax) {
             for (int e = MI_(TENJ_ADR)[t]; e < MI_(TENJ_ADR)[t + 1]; e++) Jrow(r)[MI_(TENJ_DOF)[e]] = tsign * W[L.tenj + e];
             RT[3 * r] = __int_as_float(MM_CON_LIMIT_TENDON | (t << 3)); RT[3 * r + 1] = tdist - tmargin; RT[3 * r + 2] = MF_(TENDON_INVWEIGHT0)[t];
           } else over = 1;
@@ -3001,15 +3004,38 @@ struct Engine {
     int myrows = 0;
     for (int c = 0; c < 2; c++) if (c < nc && cdist[c] < incl) myrows += rowsper;
     int base = pre_rows + rows_run + gscan_excl(myrows);
+    // Row bases.  When every contact of the chunk fits under the row bound in every env of the wave (every bench workload, always) the
+    // prefix sum above is the layout.  Otherwise the oracle's rule: contacts in pair order, one that does not fit is dropped whole and
+    // flagged, a LATER one that fits still gets rows (a condim-1 contact behind a dropped condim-3 one) -- a serial pass over the
+    // chunk's lanes, two broadcasts per lane, and rows_run carries the rows actually made.
+    int cbase[2] = {-1, -1};
+    int chunk_made = -1;                       // rows made by this chunk (group-uniform) when the serial pass ran
+    if (__ballot(base + myrows > rmax) == 0ull) {
+#pragma unroll
+      for (int c = 0; c < 2; c++)
+        if (c < nc && cdist[c] < incl) { cbase[c] = base; base += rowsper; }
+    } else {
+      const int run0 = pre_rows + rows_run;
+      int run = run0;                          // group-uniform
+      for (int l = 0; l < G; l++) {
+#pragma unroll
+        for (int c = 0; c < 2; c++) {
+          const int need = (int)bc<G>((real)((c < nc && cdist[c] < incl) ? rowsper : 0), l);
+          if (need == 0) continue;
+          if (run + need <= rmax) { if (g == l) cbase[c] = run; run += need; }
+          else over = 1;
+        }
+      }
+      chunk_made = run - run0;
+    }
     // Row table entries by the pair's lane; the Jacobian rows by ALL lanes of the group, one dof each: lane i holds its dof's
     // motion axis in registers and knows from a per-body chain mask (Aux.body_dofmask) whether dof i moves geom1's or geom2's
     // body, so a contact costs a handful of broadcasts + 4 stores per lane instead of one lane walking two kinematic chains
     // with two dependent LDS round trips per dof (11 k cycles per forward pass for the leg's foot contacts).
-    int cbase[2] = {-1, -1};
+#pragma unroll
     for (int c = 0; c < 2; c++) {
-      if (!(c < nc && cdist[c] < incl)) continue;
-      if (base + rowsper > KD().efc_rows) { over = 1; continue; }
-      cbase[c] = base;
+      if (cbase[c] < 0) continue;
+      base = cbase[c];
       made += rowsper;
       const real tran = MF_(BODY_INVWEIGHT0)[2 * b1] + MF_(BODY_INVWEIGHT0)[2 * b2];
       for (int k = 0; k < rowsper; k++) {
@@ -3017,7 +3043,6 @@ struct Engine {
         RT[3 * (base + k) + 1] = cdist[c] - incl;
         RT[3 * (base + k) + 2] = rowsper == 1 ? tran : tran + mu * mu * tran;
       }
-      base += rowsper;
     }
     {
       const int np_ = KD().npair, nv_ = KD().nv;
@@ -3096,15 +3121,15 @@ struct Engine {
         }
       }
     }
-    if (p0 + G < KD().npair) { ncon_run += gsum_i(nc); rows_run += gsum_i(myrows); }   // (wave-uniform branch; never taken with one chunk)
+    if (p0 + G < KD().npair) { ncon_run += gsum_i(nc); rows_run += chunk_made >= 0 ? chunk_made : gsum_i(myrows); }   // (wave-uniform branch; never taken with one chunk)
     }   // pair chunks
-    if (gor<G>(over)) status |= 8;   // more rows than lanes: surplus rows dropped (njmax-style warning)
+    if (gor<G>(over)) status |= 8;   // rows beyond njmax (or contacts beyond nconmax) dropped: the oracle's warning
     // rows that exist: everything ahead of the contacts up to the table size, plus the contact rows that were created.  (Counting
     // the rows of a DROPPED contact -- round 2: min(sum, efc_rows) -- left the tail rows active with whatever the row table
     // held: a garbage row descriptor indexes the solimp / solref tables out of bounds, a memory fault with the model in HBM.)
     {
       const int pre = neq + nfr + nlim + ntl;
-      nefc = (pre < KD().efc_rows ? pre : KD().efc_rows) + gsum_i(made);
+      nefc = (pre < rmax ? pre : rmax) + gsum_i(made);
     }
     {
       int w = nefc;
@@ -3570,11 +3595,16 @@ struct Engine {
     // sets iterations = 6; mm_model_set_option) MuJoCo's start rule is followed to the letter, as it is by envs without rows
     // (qacc = qacc_smooth) and in debug dumps (mm_debug_set_dump: the stage-by-stage record the tests compare with the oracle's Newton
     // path, qacc_smooth and iteration count included; the all-env scans and every rollout test run the production path).
-    no_sm = MM_SKIP_QACCSM && !a.dbg && nefc > 0 && KD().iterations >= MM_SKIP_QACCSM_MIN_ITER;
+    // The convergence argument needs a warm start the Newton iteration can start from: an env whose warm start holds a NaN, an
+    // infinity or an entry beyond mjMAXVAL (1e10, the bad-state bound) -- a caller's set_env_state / ABI rows -- follows MuJoCo's
+    // rule too, where the comparison of the two costs (NaN < x is false) falls back to qacc_smooth.
+    const bool warm_ok = gor<G>(!(m_abs(d_warm) < 1e10f)) == 0;      // (lanes g >= nv hold 0)
+    no_sm = MM_SKIP_QACCSM && !a.dbg && nefc > 0 && KD().iterations >= MM_SKIP_QACCSM_MIN_ITER && warm_ok;
     const bool wave_skip = __ballot(!no_sm) == 0ull;
     if constexpr (!SP) { if (!spg && !wave_skip) PFT(PF_FACTOR, factor(0.f)); }
     PFT(PF_ACT, passive_actuation());
-    if (!wave_skip) {
+    if (wave_skip) d_qaccsm = 0.f;     // the Gauss term's constant: never a value left over from an earlier pass
+    else {
       if constexpr (SP) PFT(PF_SOLVE0, d_qaccsm = sp_factor_solve(0.f, d_smooth));
       else {
         if (spg) { if constexpr (SPG) PFT(PF_SOLVE0, d_qaccsm = spg_factor_solve(0.f, d_smooth)); }
