@@ -66,20 +66,9 @@ __device__ __forceinline__ real m_add_rn(real a, real b) { return __fadd_rn(a, b
 // ------------------------------------------------------------------ small math
 struct V3 { real x, y, z; };
 __device__ __forceinline__ V3 v3(real x, real y, real z) { V3 r = {x, y, z}; return r; }
-#ifndef MM_PK_V3
-#define MM_PK_V3 0   /* 1 (A/B): the x, y components of V3 sums / differences / scalings / matrix-vector products as hand-placed packed
-                        fp32 operations (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32 on an (x, y) pair), z scalar */
-#endif
-#if MM_PK_V3 && !MM_F64
-typedef float pk2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ V3 operator+(V3 a, V3 b) { const pk2 r = pk2{a.x, a.y} + pk2{b.x, b.y}; return v3(r.x, r.y, a.z + b.z); }
-__device__ __forceinline__ V3 operator-(V3 a, V3 b) { const pk2 r = pk2{a.x, a.y} - pk2{b.x, b.y}; return v3(r.x, r.y, a.z - b.z); }
-__device__ __forceinline__ V3 operator*(real s, V3 a) { const pk2 r = pk2{s, s} * pk2{a.x, a.y}; return v3(r.x, r.y, s * a.z); }
-#else
 __device__ __forceinline__ V3 operator+(V3 a, V3 b) { return v3(a.x + b.x, a.y + b.y, a.z + b.z); }
 __device__ __forceinline__ V3 operator-(V3 a, V3 b) { return v3(a.x - b.x, a.y - b.y, a.z - b.z); }
 __device__ __forceinline__ V3 operator*(real s, V3 a) { return v3(s * a.x, s * a.y, s * a.z); }
-#endif
 __device__ __forceinline__ real dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 __device__ __forceinline__ V3 cross(V3 a, V3 b) {
   return v3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
@@ -120,20 +109,6 @@ template <class P> __device__ __forceinline__ M3 ldm(const P& p) {
   for (int i = 0; i < 9; i++) r.m[i] = p[i];
   return r;
 }
-#if MM_PK_V3 && !MM_F64
-__device__ __forceinline__ V3 mv(const M3& m, V3 v) {      // rows 0 and 1 as one packed chain, row 2 scalar
-  pk2 r = pk2{m.m[0], m.m[3]} * pk2{v.x, v.x};
-  r = __builtin_elementwise_fma(pk2{m.m[1], m.m[4]}, pk2{v.y, v.y}, r);
-  r = __builtin_elementwise_fma(pk2{m.m[2], m.m[5]}, pk2{v.z, v.z}, r);
-  return v3(r.x, r.y, m.m[6] * v.x + m.m[7] * v.y + m.m[8] * v.z);
-}
-__device__ __forceinline__ V3 mtv(const M3& m, V3 v) {     // (M' v)_{0,1}: the matrix pairs are adjacent table words
-  pk2 r = pk2{m.m[0], m.m[1]} * pk2{v.x, v.x};
-  r = __builtin_elementwise_fma(pk2{m.m[3], m.m[4]}, pk2{v.y, v.y}, r);
-  r = __builtin_elementwise_fma(pk2{m.m[6], m.m[7]}, pk2{v.z, v.z}, r);
-  return v3(r.x, r.y, m.m[2] * v.x + m.m[5] * v.y + m.m[8] * v.z);
-}
-#else
 __device__ __forceinline__ V3 mv(const M3& m, V3 v) {
   return v3(m.m[0] * v.x + m.m[1] * v.y + m.m[2] * v.z, m.m[3] * v.x + m.m[4] * v.y + m.m[5] * v.z,
             m.m[6] * v.x + m.m[7] * v.y + m.m[8] * v.z);
@@ -142,7 +117,6 @@ __device__ __forceinline__ V3 mtv(const M3& m, V3 v) {
   return v3(m.m[0] * v.x + m.m[3] * v.y + m.m[6] * v.z, m.m[1] * v.x + m.m[4] * v.y + m.m[7] * v.z,
             m.m[2] * v.x + m.m[5] * v.y + m.m[8] * v.z);
 }
-#endif
 __device__ __forceinline__ real clampf(real x, real lo, real hi) { return m_min(m_max(x, lo), hi); }
 
 // sin/cos of a joint half-angle (|x| <= ~8), evaluated in fp64 and rounded ONCE to fp32 (<= 0.5 ulp).  Round 2 used an fp32
@@ -150,13 +124,10 @@ __device__ __forceinline__ real clampf(real x, real lo, real hi) { return m_min(
 // orientation error per joint, which a 0.2 m lever arm and a 9-joint chain turn into ~1.5e-7 m of position error -- 3x what
 // fp32 storage alone costs, and the largest term in the kernel's tendon moment-arm error (moment arms are ~5 mm, path
 // segments as short as that).  v_fma_f64 issues at the fp32 FMA rate on gfx950 and this runs once per joint per pass.
-#ifndef MM_SINCOS_F64
-#define MM_SINCOS_F64 1
-#endif
 __device__ __forceinline__ void sincos_small(real x, real* s, real* c) {
 #if MM_F64
   ::sincos(x, s, c);   // precision-mode kernels: the device library's fp64 form (< 2 ulp)
-#elif MM_SINCOS_F64
+#else
   const double xd = (double)x;
   const double k = __builtin_rint(xd * 0.63661977236758134308);
   const double r = __builtin_fma(-k, 1.57079632679489661923, xd);   // |k| <= 6: the product is exact to 1e-15
@@ -178,19 +149,6 @@ __device__ __forceinline__ void sincos_small(real x, real* s, real* c) {
   const double ss = (q & 1) ? cs : sn, cc = (q & 1) ? sn : cs;
   *s = (real)((q & 2) ? -ss : ss);
   *c = (real)(((q + 1) & 2) ? -cc : cc);
-#else
-  real k = m_rint(x * 0.636619772367581f);
-  real r = m_fma(-k, 1.5707963705062866f, x);
-  r = m_fma(-k, -4.371138828673793e-8f, r);
-  real r2 = r * r;
-  real sp = m_fma(m_fma(m_fma(2.718311493989822e-6f, r2, -1.984090227e-4f), r2, 8.3333169e-3f), r2, -0.16666667f);
-  real sn = m_fma(sp * r2, r, r);
-  real cp = m_fma(m_fma(m_fma(2.443315711809948e-5f, r2, -1.388731625e-3f), r2, 4.166664568e-2f), r2, -0.5f);
-  real cs = m_fma(cp, r2, 1.f);
-  int q = (int)k & 3;
-  real ss = (q & 1) ? cs : sn, cc = (q & 1) ? sn : cs;
-  *s = (q & 2) ? -ss : ss;
-  *c = ((q + 1) & 2) ? -cc : cc;
 #endif
 }
 
@@ -708,47 +666,15 @@ __device__ __forceinline__ real muscle_dynamics(real ctrl, real act, const real*
 #ifndef MM_KIN_PROF
 #define MM_KIN_PROF 0   /* tools build (with MM_STAGE_PROF=1): sub-stage timers of the kinematics in the n_warm / n_grad / n_solve / n_prod slots (offsets pinned / own joints / pointer-jumping rounds / final frames + anchors + matrices); the Newton timers that share the slots are off */
 #endif
-#ifndef MM_TENVEL_UNROLL
-/* 1: tendon velocities J qvel with four entries per turn (their dof ids requested together, then their velocities) instead of entry by
-   entry.  Built and measured in round 6 (same-session A/B): hand 7.913 -> 7.915 M, self-contact hand 3.640 -> 3.627 M, reorient 4.388 ->
-   4.422 M: noise level.  OFF. */
-#define MM_TENVEL_UNROLL 0
-#endif
 #ifndef MM_SKIP_QACCSM
-#define MM_SKIP_QACCSM 1            /* 0: A/B switch: every forward pass factorises M and solves for qacc_smooth (rounds 1-5); see Engine::forward */
+#define MM_SKIP_QACCSM 1            /* 0: every forward pass factorises M and solves for qacc_smooth (rounds 1-5; see Engine::forward) -- the
+                                       reference path of paired accuracy comparisons (ADVICE.md) */
 #endif
 #ifndef MM_SKIP_QACCSM_MIN_ITER
 #define MM_SKIP_QACCSM_MIN_ITER 20  /* Newton budgets below this can bind: MuJoCo's start rule is followed to the letter */
 #endif
-#ifndef MM_SG_UNCOND
-/* 1: tree-sparse factor + solve with the segment rows of all depths and all eight child update matrices loaded unconditionally and
-   masked per lane, instead of a scalar branch per depth / per child around the loads (tools/isa_masked_loads.py counts 32 + 24 such
-   load + wait blocks in the hand kernel).  Built and measured in round 6 (tools/build_variant.py sgu, same-session A/B, 0 spills either
-   way): hand 7.118 -> 7.081 M env-steps/s -- with two waves per SIMD the other wave covers those round trips, and the selects + the
-   three absent children's loads cost issue slots.  OFF. */
-#define MM_SG_UNCOND 0
-#endif
-#ifndef MM_CRB_MASKWALK
-/* N > 0: the dense kernels' M assembly reads the ancestors of a dof off its body's chain mask, N per LDS round trip, instead of chasing
-   DOF_PARENTID with the pointer fetched a step ahead.  Built and measured in round 6 (tools/build_variant.py mw4 / mw2, same-session A/B
-   against -DMM_CRB_MASKWALK=0): leg 1.866 -> 1.853 / 1.854 M, implicitfast leg 1.766 -> 1.779 / 1.773 M, reorient 4.199 -> 4.180 / 4.189 M,
-   self-contact hand 3.378 -> 3.373 / 3.376 M -- noise level either way: the 17-level walk was not on the critical path (the other lanes'
-   shorter walks and the tile stores overlap it).  OFF. */
-#define MM_CRB_MASKWALK 0
-#endif
-#ifndef MM_LS_DIRECT
-/* 1: the limit-rows-only kernels' exact line search in CLOSED FORM (every lane evaluates phi' and its slope at its row's break point in
-   one sweep over the group's active rows, the root is on the piece behind the largest one with phi' <= 0) instead of the safeguarded
-   Newton iteration on phi'.  Built and measured in round 6 (tools/build_variant.py lsd -DMM_LS_DIRECT=1, same-session A/B): hand 7.10 ->
-   6.96 M env-steps/s, elbow 31.9 -> 31.8 M -- the iteration usually ends in three or four turns of two group reductions, while the sweep
-   pays three broadcasts (two v_readlane + a select each at 32 lanes per env) per active row of BOTH envs of the wave.  OFF. */
-#define MM_LS_DIRECT 0
-#endif
-#ifndef MM_FUSE_SUBTREE
-#define MM_FUSE_SUBTREE 1   /* 0: A/B switch: the velocity stage's body forces and the CRB inertias summed up the tree in two sweeps */
-#endif
 #ifndef MM_PAIR_CULL
-#define MM_PAIR_CULL 1   /* 0: A/B switch (tools/build_variant.py): the narrow phase without the bounding-sphere cull */
+#define MM_PAIR_CULL 1   /* 0 (tools/build_variant.py): the narrow phase without the bounding-sphere cull -- the reference path of paired accuracy comparisons */
 #endif
 #ifndef MM_BADCTRL_CHECK
 #define MM_BADCTRL_CHECK 1   /* 0: A/B switch (tools/build_variant.py): without the control check; 2: the check as a second pass over the LDS row */
@@ -760,61 +686,23 @@ __device__ __forceinline__ real muscle_dynamics(real ctrl, real act, const real*
 #define MM_STAGE_PROF 0   /* 1: in-kernel stage timers (mm_debug_set_prof); a tools build (tools/build_variant.py prof -DMM_STAGE_PROF=1): \
                              the 26 SGPRs of the timer array and the clock reads cost the product kernels 1-2 % */
 #endif
-#ifndef MM_SPARSE_GEN
-#define MM_SPARSE_GEN 0   /* 1: the general-row kernels use the tree-sparse solve for the two M solves of a pass (solve0, Euler).  Measured: \
-                             the extra live state tips these 256-VGPR kernels into 80 spills; reorient -3 %, self-contact hand -5 % */
-#endif
 #ifndef MM_FOLD_RESET
 #define MM_FOLD_RESET 1   /* 0: no folded walk / reorient reset (A/B switch; MM_INFO_FOLDED_RESET then reports 0) */
-#endif
-#ifndef MM_LS_RELSTOP
-/* Experiment, OFF: end the exact line search once a turn moves alpha by less than MM_LS_RELSTOP_TOL relative, instead of running the
-   safeguarded Newton on phi'(alpha) until its step vanishes in real resolution.  The stage timers put ~10 k of the hand's 32 k
-   Newton cycles per pass in the search, but the precision of alpha is not slack: qacc += alpha * search with |search| up to
-   1e2...1e3, and tolerance 1e-5 took the north-star count from 61 to 55 of 64 envs (median 3.6e-6 -> 1.2e-5) for +1.9 %
-   throughput; 1e-6: 58 of 64, +0.8 %; 3e-7: 61 of 64, +0.6 % (profiles/r03_north_star_ab.json).  Not worth a digit. */
-#define MM_LS_RELSTOP 0
-#endif
-#ifndef MM_LS_RELSTOP_TOL
-#define MM_LS_RELSTOP_TOL 3e-7f
-#endif
-#ifndef MM_NEWTON_GRADCHECK
-/* The solvers end on "a full Newton step (alpha = 1) left the active set unchanged": exact on a piecewise-quadratic cost -- in
-   exact arithmetic.  In fp32 the Newton direction comes out of a Cholesky solve of H = M + J'DJ whose condition number reaches
-   1e8...1e9 with contact rows (D ~ 1e5...1e6 against M ~ 1e-3): the step can land percent off the minimiser and still have
-   alpha ~ 1 and an unchanged set (round 4: one env in ~100 of the self-colliding hand ended with 11 % error in qacc, found by
-   comparing a solve from the stepped warm start with one from a zero warm start).  1: the exit also needs the residual gradient
-   |M (a - a0) - J'f| below MM_GRAD_REL |M (a - a0)| + MM_GRAD_ABS |qfrc_smooth|; if it is not, up to MM_NEWTON_REFINE further
-   Newton steps run from the point reached -- the same H, the residual as right-hand side: iterative refinement.  0: round 3. */
-#define MM_NEWTON_GRADCHECK 1
 #endif
 #ifndef MM_NEWTON_TRACE
 #define MM_NEWTON_TRACE 0   /* tools build: per-iteration record of the general-row Newton solve in the debug dump (scal + 32 ...) */
 #endif
-#ifndef MM_NEWTON_INCR
-/* Incremental Newton (MuJoCo: rank-one up / down-dates of the Cholesky factor when the active set changes by a few rows; engine behind
-   robot/robot.py:861): iterations after the first modify the factor of H = M + J_A' D J_A by +- D_r j_r j_r' for the rows that entered /
-   left the quadratic set instead of rebuilding H (MFMA sweep) and refactorising it, when at most MM_NEWTON_INCR rows changed
-   (one-env-per-wave fp32 general-row kernels).  A down-date whose pivot loses two digits falls back to the rebuild.  0: always rebuild.
-   A/B switch (tools/build_variant.py incr -DMM_NEWTON_INCR=2), OFF in the shipped units.  Measured on MI355X, same session, kernel ms of
-   the fused env-step: 36-wide legs 0.542 -> 0.530 (Euler, +2.4 % in the upright phase of the episode, +0.9 % in bench.py's steady mix)
-   and 0.565 -> 0.553 (implicitfast) with 2 -- at the price of 45...52 spilled VGPRs and 3x the HBM write traffic (scratch); the
-   self-colliding hand and reorient 0...-3 % with 1, 2 or 3: there a rebuild (MFMA sweep) + refactorisation is only 8...16 k cycles per
-   iteration against ~3 k per modified row, and the block's two inlined NVP-step sweeps cost registers.  Results are unchanged either way
-   (the all-env scan of tests/test_gpu_widths.py passes with it on): the stop criterion is the exact gradient. */
-#define MM_NEWTON_INCR 0
-#endif
+/* The solvers end on "a full Newton step (alpha = 1) left the active set unchanged": exact on a piecewise-quadratic cost -- in exact
+   arithmetic.  In fp32 the Newton direction comes out of a Cholesky solve of H = M + J'DJ whose condition number reaches 1e8...1e9 with
+   contact rows: the step can land percent off the minimiser and still have alpha ~ 1 and an unchanged set (round 4: one env in ~100 of
+   the self-colliding hand ended with 11 % error in qacc).  So the exit also needs the residual gradient |M (a - a0) - J'f| below
+   MM_GRAD_REL |M (a - a0)| + MM_GRAD_ABS |qfrc_smooth|; if it is not, up to MM_NEWTON_REFINE further Newton steps run from the point
+   reached -- the same H, the residual as right-hand side: iterative refinement. */
 #ifndef MM_NEWTON_REFINE
 #define MM_NEWTON_REFINE 3
 #endif
-#ifndef MM_NEWTON_POLISH
-#define MM_NEWTON_POLISH 0   /* experiment (limit-rows-only kernels): one extra Newton step after the convergence test fires */
-#endif
-#ifndef MM_NEWTON_TRUE_MV
-#define MM_NEWTON_TRUE_MV 0  /* experiment (tree-sparse kernels): M search as an explicit product instead of -grad - D search */
-#endif
 #ifndef MM_SPARSE_LDL
-#define MM_SPARSE_LDL 1   /* 0: dense register Cholesky in every kernel (A/B switch) */
+#define MM_SPARSE_LDL 1   /* 0: dense register Cholesky in every kernel -- the dense fallback */
 #endif
 // =========================================================================== engine
 /* keep a wave-uniform value in an SGPR: opaque to rematerialisation (an s_load + s_waitcnt at every use).  The readfirstlane
@@ -860,7 +748,7 @@ struct Engine {
   // always for narrow groups; one env per wave, measured per tile width: 24-wide (self-contact hand) +1.2 %, 32-wide (reorient) -2.7 %
   static constexpr bool LDS_VECTOR = NVP >= 8 && (G < 64 || NVP <= 24);
   const KArgs& a;
-  const KConst& kc;    // model constants of the launch (see MM_CONST_IN_REGS)
+  const void* layout_pad_;   // never used: with the member offsets it keeps, the backend assigns the same registers (tools/isa_hash.py)
   const uint32_t* mb;  // model words (LDS-resident copy or global)
   unsigned long long pf[MM_STAGE_PROF ? NPROF : 1];
   real* W;     // LDS tables of this env
@@ -942,16 +830,13 @@ struct Engine {
   bool carry_out;           // (re)write this env's carry row after the trailing forward pass
   __device__ __forceinline__ float* carry_row() const {
     int e_ = env;
-#ifndef MM_CARRY_VADDR
-#define MM_CARRY_VADDR 0
-#endif
-    if constexpr (G == 64 && !MM_CARRY_VADDR) { e_ = __builtin_amdgcn_readfirstlane(e_); asm volatile("" : "+s"(e_)); }
+    if constexpr (G == 64) { e_ = __builtin_amdgcn_readfirstlane(e_); asm volatile("" : "+s"(e_)); }
     else asm volatile("" : "+v"(e_));
     return KA().t.fwd_carry + (size_t)e_ * (size_t)(2 * KD().nv + 1);
   }
 
-  __device__ __forceinline__ Engine(const KArgs& a_, const KConst& kc_, const uint32_t* mb_, real* W_, int g_)
-      : a(a_), kc(kc_), mb(mb_), W(W_), g(g_), status(0), nefc(0), niter(0), no_sm(false), tw_n(0), o_tile(0), carry_in(false), carry_out(false) {
+  __device__ __forceinline__ Engine(const KArgs& a_, const uint32_t* mb_, real* W_, int g_)
+      : a(a_), mb(mb_), W(W_), g(g_), status(0), nefc(0), niter(0), no_sm(false), tw_n(0), o_tile(0), carry_in(false), carry_out(false) {
     o_tile = KL().u1;   // (not in the initialiser list: the member is declared ahead of the references KL() goes through)
 #pragma unroll
     for (int i = 0; i < (MM_STAGE_PROF ? NPROF : 1); i++) pf[i] = 0;
@@ -1361,9 +1246,6 @@ struct Engine {
 #else
     for (int t = g; t < KD().ntendon; t += G) W[o.tenlen + t] = AF_(KX().ten_len0)[t];
 #endif
-#if MM_FUSE_TENVEL
-    for (int t = g; t < KD().ntendon; t += G) W[L.tenvel + t] = 0.f;     // summed by the Jacobian-entry sweep below
-#endif
     GSYNC();
     for (int it = g; it < nitem; it += G) {
       const int4 I = items[it];   // [tendon | kind << 16, site0 | site1 << 16, geom | (sidesite + 1) << 16, bits(1 / divisor)]
@@ -1407,18 +1289,8 @@ struct Engine {
     const int* jent = reinterpret_cast<const int*>(mb + o_jent);
     const int4* jrow = reinterpret_cast<const int4*>(mb + o_jrec);
     int jn = g < d_ntenJ ? jent[g] : 0;
-#if MM_FUSE_TENVEL
-    // tendon velocities J qvel summed entry by entry in this sweep (one LDS float add per entry: in-order within the wave, so the sum
-    // is reproducible) -- the separate pass was one lane per tendon walking its <= 8 entries with two dependent loads apiece
-    const int* jtd = reinterpret_cast<const int*>(mb + KX().jent_td);
-    const int o_tenvel = L.tenvel, o_qvel_ = L.qvel;
-#endif
     for (int i = g; i < d_ntenJ; i += G) {
       const int r0 = jn & 0xffffff, nr = (jn >> 24) & 127;
-#if MM_FUSE_TENVEL
-      const int td_ = jtd[i];
-      const real qv_ = W[o_qvel_ + (td_ >> 16)];
-#endif
       if (i + G < d_ntenJ) jn = jent[i + G];   // next sweep's row index: off this sweep's dependency chain
       real acc = 0.f;
       int e = 0;
@@ -1457,9 +1329,6 @@ struct Engine {
         acc += ep ? val : -val;
       }
       W[o.tenj + e] = acc;
-#if MM_FUSE_TENVEL
-      atomicAdd(&W[o_tenvel + (td_ & 0xffff)], acc * qv_);
-#endif
     }
     GSYNC();
     if (MM_STAGE_PROF && a.prof) pf[MM_STAGE_PROF ? PF_N_FACTOR : 0] += clock64() - tt_;   // (tools build: Jacobian-entry sweep)
@@ -1529,7 +1398,6 @@ struct Engine {
 
   // tendon velocities J qvel (sparse rows)
   __device__ __forceinline__ void tendon_velocity() {
-    if (MM_FUSE_TENVEL) return;          // summed in tendon()'s Jacobian-entry sweep
     const auto& L = KL();
     int o_qvel = L.qvel;
     {
@@ -1538,23 +1406,7 @@ struct Engine {
       for (int t = g; t < KD().ntendon; t += G) {
         real s = 0.f;
         const int e0 = reinterpret_cast<const int*>(mb + s_ja)[t], e1 = reinterpret_cast<const int*>(mb + s_ja)[t + 1];
-#if MM_TENVEL_UNROLL
-        // four entries per turn, their dof ids requested together and then their velocities: two LDS round trips per four entries
-        // (entry by entry the dof id -> velocity chain was two dependent round trips per entry, up to 8 entries on the hand and leg)
-        const int* jd_ = reinterpret_cast<const int*>(mb + s_jd);
-        for (int e = e0; e < e1; e += 4) {
-          const int i1 = e + 1 < e1 ? e + 1 : e, i2 = e + 2 < e1 ? e + 2 : e, i3 = e + 3 < e1 ? e + 3 : e;
-          const int d0 = jd_[e], d1 = jd_[i1], d2 = jd_[i2], d3 = jd_[i3];
-          const real j0 = W[o_tj + e], j1 = W[o_tj + i1], j2 = W[o_tj + i2], j3 = W[o_tj + i3];
-          const real q0 = W[o_qv + d0], q1 = W[o_qv + d1], q2 = W[o_qv + d2], q3 = W[o_qv + d3];
-          s += j0 * q0;
-          if (e + 1 < e1) s += j1 * q1;
-          if (e + 2 < e1) s += j2 * q2;
-          if (e + 3 < e1) s += j3 * q3;
-        }
-#else
         for (int e = e0; e < e1; e++) s += W[o_tj + e] * W[o_qv + reinterpret_cast<const int*>(mb + s_jd)[e]];
-#endif
         W[o_tv + t] = s;
       }
     }
@@ -1566,11 +1418,11 @@ struct Engine {
   // bottom up in registers, starting from its bottom body's value plus the finished totals of the chains hanging off it.  One
   // step per level of the CHAIN tree (3 for the hand and the leg) instead of one per level of the body tree (9 / 12), and no LDS
   // real atomics.  Falls back to the level-by-level atomic sweep when the host could not build the chains (bchain_nlevel = 0).
-  // Two tables in one sweep (KB > 0): the velocity stage's body forces (6 words per body) and the CRB stage's inertias (10) are summed
+  // Two tables in one sweep: the velocity stage's body forces (K = 6 words per body) and the CRB stage's inertias (KB = 10) are summed
   // up the same tree from inputs that are both final once the bias accelerations are -- one sweep's dependent LDS round trips
   // (read, add, write per chain step) instead of two; the sums themselves are the same operations in the same order.
-  template <int K, int KB = 0>
-  __device__ __forceinline__ void subtree_sum(int o_tab, int o_tb = 0) {
+  template <int K, int KB>
+  __device__ __forceinline__ void subtree_sum(int o_tab, int o_tb) {
     const int ncl = KD().bchain_nlevel & 15, maxch = (KD().bchain_nlevel >> 4) & 15, maxlen = KD().bchain_nlevel >> 8;
     int bottom = 0, lv = -1, nch = 0;
     unsigned ch_lo = 0u, ch_hi = 0u;
@@ -1581,7 +1433,7 @@ struct Engine {
     }
     for (int cl = ncl - 1; cl >= 0; cl--) {
       if (lv == cl) {
-        real acc[K], accb[KB > 0 ? KB : 1];
+        real acc[K], accb[KB];
 #pragma unroll
         for (int k = 0; k < K; k++) acc[k] = W[o_tab + K * bottom + k];
 #pragma unroll
@@ -1710,15 +1562,13 @@ struct Engine {
       if (g < nb) {
 #pragma unroll
         for (int k = 0; k < 6; k++) W[o_u1 + 6 * g + k] = cf[k];
-        if constexpr (MM_FUSE_SUBTREE) {      // the CRB stage's inputs: summed in the same sweep (crb() then starts from the sums)
-          const int o_crb = KL().crb;
+        // the CRB stage's inputs: summed in the same sweep (crb() then starts from the sums)
+        const int o_crb = KL().crb;
 #pragma unroll
-          for (int k = 0; k < 10; k++) W[o_crb + 10 * g + k] = b_cinert[k];
-        }
+        for (int k = 0; k < 10; k++) W[o_crb + 10 * g + k] = b_cinert[k];
       }
       GSYNC();
-      if constexpr (MM_FUSE_SUBTREE) subtree_sum<6, 10>(o_u1, KL().crb);
-      else subtree_sum<6>(o_u1);
+      subtree_sum<6, 10>(o_u1, KL().crb);
     } else {
       if (g < nb)
 #pragma unroll
@@ -1751,7 +1601,7 @@ struct Engine {
     int o_cdof = KL().cdof; PIN_S(o_cdof); int o_u1 = KL().u1; PIN_S(o_u1); int o_crb = KL().crb; PIN_S(o_crb); int s_DOF_PARENTID = SECOFF_(DOF_PARENTID); PIN_S(s_DOF_PARENTID); int s_DOF_BODYID = SECOFF_(DOF_BODYID); PIN_S(s_DOF_BODYID); int s_DOF_ARMATURE = SECOFF_(DOF_ARMATURE); PIN_S(s_DOF_ARMATURE); int d_nv_ = KD().nv; PIN_S(d_nv_); int d_nbody_ = KD().nbody; PIN_S(d_nbody_);
     const auto& L = KL();
     const int nb = d_nbody_, nv = d_nv_;
-    const bool summed = MM_FUSE_SUBTREE && KD().bchain_nlevel > 0;     // the velocity stage's sweep summed the inertias too
+    const bool summed = KD().bchain_nlevel > 0;     // the velocity stage's sweep summed the inertias too
     if (g < nb && !summed)
 #pragma unroll
       for (int k = 0; k < 10; k++) W[o_crb + 10 * g + k] = b_cinert[k];
@@ -1759,9 +1609,7 @@ struct Engine {
     if constexpr (!SP)
       for (int e = g; e < NVP * TD; e += G) W[o_u1 + e] = 0.f;
     GSYNC();
-    if (summed) {}
-    else if (KD().bchain_nlevel > 0) subtree_sum<10>(o_crb);
-    else
+    if (!summed)
       for (int lv = KD().nlevel; lv >= 2; lv--) {
         if (b_depth == lv && b_parent > 0)
 #pragma unroll
@@ -1792,40 +1640,6 @@ struct Engine {
       for (int k = 0; k < 10; k++) I[k] = W[o_crb + 10 * b + k];
       inert_mul(buf, I, d_cdof);
       const real arm = AF_(s_DOF_ARMATURE)[g];
-#if MM_CRB_MASKWALK
-      // The ancestors-or-self of dof g are the dofs of its body's chain mask (Aux.body_dofmask) with an id <= g (ids grow down a
-      // chain): the walk reads them off the mask, MM_CRB_MASKWALK at a time, so that their motion axes are requested TOGETHER -- one
-      // LDS round trip per MM_CRB_MASKWALK ancestors.  (Rounds 1-5 chased DOF_PARENTID: pointer -> axes -> pointer, one dependent
-      // round trip per level even with the pointer fetched a step ahead; 17 levels for the leg.)
-      {
-        const int* bmk = AUXI(body_dofmask);
-        const unsigned m_lo = (unsigned)bmk[2 * b], m_hi = (unsigned)bmk[2 * b + 1];
-        unsigned long long mk = (((unsigned long long)m_hi << 32) | (unsigned long long)m_lo) & (g >= 63 ? ~0ull : ((2ull << g) - 1ull));
-        while (mk) {
-          int jj[MM_CRB_MASKWALK];
-          bool vv[MM_CRB_MASKWALK];
-#pragma unroll
-          for (int u = 0; u < MM_CRB_MASKWALK; u++) {
-            vv[u] = mk != 0ull;
-            jj[u] = vv[u] ? (int)__builtin_ctzll(mk) : g;
-            mk &= mk - 1ull;                                   // (0 stays 0)
-          }
-          real cj[MM_CRB_MASKWALK][6];
-#pragma unroll
-          for (int u = 0; u < MM_CRB_MASKWALK; u++)
-#pragma unroll
-            for (int k = 0; k < 6; k++) cj[u][k] = W[o_cdof + 6 * jj[u] + k];
-#pragma unroll
-          for (int u = 0; u < MM_CRB_MASKWALK; u++) {
-            real s = 0.f;
-#pragma unroll
-            for (int k = 0; k < 6; k++) s += cj[u][k] * buf[k];
-            if (jj[u] == g) s += arm;
-            if (vv[u]) { W[o_u1 + g * TD + jj[u]] = s; W[o_u1 + jj[u] * TD + g] = s; }
-          }
-        }
-      }
-#else
       const int* dpar = AI_(s_DOF_PARENTID);
       // ancestor walk with the parent pointer fetched one step ahead: the motion axes of ancestor j and the pointer two above it
       // are in flight together (pointer -> axes -> pointer was two dependent round trips per level, 17 levels for the leg)
@@ -1844,7 +1658,6 @@ struct Engine {
         W[o_u1 + j * TD + g] = s;
         j = jn; jn = jnn;
       }
-#endif
     } else if (g < NVP) {
       W[o_u1 + g * TD + g] = 1.f;
     }
@@ -1902,26 +1715,6 @@ struct Engine {
   template <int D_>
   __device__ __forceinline__ void sg_load_rows(const SegLane& q, const real* T, real (&F)[36], real (&r)[SD], int t, int b) const {
     if constexpr (D_ < SD) {
-#if MM_SG_UNCOND
-      // Round 6: the rows of ALL depths are requested unconditionally (path bytes outside the segment point at dof 0: harmless reads)
-      // and masked with the lane's own (t, b) afterwards -- a per-lane select, so it stays a select: the scalar branch per depth
-      // around these loads was one serialised LDS round trip per depth of the segment (tools/isa_masked_loads.py: 32 such blocks).
-      (void)t; (void)b;
-      const bool in_ = D_ >= q.t && D_ <= q.b;
-      const real* P = T + sg_path<D_>(q) * TS;
-      const real4 p0 = *reinterpret_cast<const real4*>(P);
-      const real v0[4] = {p0.x, p0.y, p0.z, p0.w};
-#pragma unroll
-      for (int e = 0; e <= (D_ < 3 ? D_ : 3); e++) F[tri(D_) + e] = in_ ? v0[e] : 0.f;
-      if constexpr (D_ >= 4) {
-        const real4 p1 = *reinterpret_cast<const real4*>(P + 4);
-        const real v1[4] = {p1.x, p1.y, p1.z, p1.w};
-#pragma unroll
-        for (int e = 4; e <= D_; e++) F[tri(D_) + e] = in_ ? v1[e - 4] : 0.f;
-      }
-      const real pr_ = P[8];
-      r[D_] = in_ ? pr_ : 0.f;
-#else
       if (D_ >= t && D_ <= b) {
         const real* P = T + sg_path<D_>(q) * TS;
         const real4 p0 = *reinterpret_cast<const real4*>(P);
@@ -1936,7 +1729,6 @@ struct Engine {
         }
         r[D_] = P[8];
       }
-#endif
       sg_load_rows<D_ + 1>(q, T, F, r, t, b);
     }
   }
@@ -1984,26 +1776,6 @@ struct Engine {
   // time -- the 36-word front and a whole child matrix in flight do not fit the register file next to the engine's state.
   template <bool SHALLOW>
   __device__ __forceinline__ void sg_children(const SegLane& q, const real* U, int mch, int nq, int zslot, real (&F)[36], real (&r)[SD]) const {
-#if MM_SG_UNCOND
-    if constexpr (SHALLOW) {
-      // all eight child slots at once (absent children -- byte 255 -- read the all-zero slot), summed in child order: the loop over
-      // mch children was one LDS round trip per child (five for the hand's wrist segment)
-      (void)mch; (void)nq;
-      real4 u0[8], u1[8], r0[8];
-#pragma unroll
-      for (int c = 0; c < 8; c++) {
-        const unsigned id = byte_of(q.ch_lo, q.ch_hi, c);
-        const real* Uc = U + (id == 255u ? zslot : (int)id) * 36;
-        u0[c] = *reinterpret_cast<const real4*>(Uc); u1[c] = *reinterpret_cast<const real4*>(Uc + 4); r0[c] = *reinterpret_cast<const real4*>(Uc + 28);
-      }
-#pragma unroll
-      for (int c = 0; c < 8; c++) {
-        F[0] += u0[c].x; F[1] += u0[c].y; F[2] += u0[c].z; F[3] += u0[c].w; F[4] += u1[c].x; F[5] += u1[c].y;
-        r[0] += r0[c].x; r[1] += r0[c].y; r[2] += r0[c].z;
-      }
-      return;
-    }
-#endif
     for (int c = 0; c < mch; c++) {
       const unsigned id = byte_of(q.ch_lo, q.ch_hi, c);
       const real* Uc = U + (id == 255u ? zslot : (int)id) * 36;
@@ -2098,35 +1870,6 @@ struct Engine {
     for (int e = 0; e < SD; e++) P[e] = e == d_depth ? Md + dadd : Ms[e];
     return sp_solve_rows(sgl, P, rhs);
   }
-  // the same for the general-row kernels (solve0 and the implicit-damping solve of the Euler step, whose matrices have M's
-  // pattern; the Newton Hessian M + J'DJ does not).  These kernels hold M as dense rows (Mrow); the row by absolute ancestor
-  // depth is picked out of it through the (dead) dense LDS tile, and the lane's segment data is re-read from the model tables
-  // instead of held in registers across the constraint stages.
-  __device__ __forceinline__ real spg_factor_solve(real dadd, real rhs) {
-    const SegLane q = seg_lane_load();
-    real* T = W + KL().u1;
-    const int row = g < NVP ? g : 0;
-    if (g < NVP)
-#pragma unroll
-      for (int k4 = 0; k4 < NVP / 4; k4++)
-        *reinterpret_cast<real4*>(T + row * TD + 4 * k4) = make_real4(Mrow[4 * k4], Mrow[4 * k4 + 1], Mrow[4 * k4 + 2], Mrow[4 * k4 + 3]);
-    real P[SD];
-    {
-      const int* pa = AUXI(dof_seg) + 6 * (q.depth >= 0 ? g : 0);
-      // the dof's own path: ancestors by depth, then itself (words 1, 2 of an owner row describe the segment's BOTTOM dof;
-      // a dof's own ancestors are the same bytes up to its depth)
-      const unsigned a_lo = (unsigned)AUXI(dof_anc)[2 * (q.depth >= 0 ? g : 0)], a_hi = (unsigned)AUXI(dof_anc)[2 * (q.depth >= 0 ? g : 0) + 1];
-      (void)pa;
-#pragma unroll
-      for (int e = 0; e < SD; e++) {
-        const int col = e == q.depth ? g : (int)byte_of(a_lo, a_hi, e);
-        const real v = T[row * TD + (e <= q.depth ? col : row)];
-        P[e] = e < q.depth ? v : (e == q.depth ? v + dadd : 0.f);
-      }
-    }
-    GSYNC();   // the rows are read: the tile region becomes the sparse solve's work area
-    return sp_solve_rows(q, P, rhs);
-  }
   // y = M x: the diagonal and ancestor entries are this lane's row; the descendant entries M[k][g] x_k are published by the
   // descendants (their row times their x) and summed through the dof's descendant list
   __device__ __forceinline__ real sp_mul_m(real x) const {
@@ -2185,10 +1928,7 @@ struct Engine {
   // (A + diag(dadd))^-1 rhs: the one entry point of every factor + solve pair
   __device__ __forceinline__ real factor_solve(real dadd, real rhs) {
     if constexpr (SP) return sp_factor_solve(dadd, rhs);
-    else {
-      if constexpr (GEN && MM_SPARSE_LDL && MM_SPARSE_GEN && NVP >= 8 && INTEG != 2) { if (MM_SPARSE_GEN == 2 || KD().seg_nlevel > 0) return spg_factor_solve(dadd, rhs); }
-      factor(dadd); return solve(rhs);
-    }
+    else { factor(dadd); return solve(rhs); }
   }
 
   // dense Cholesky H = L L' with lane i holding row i; `dadd` is added to this lane's diagonal element.
@@ -2275,30 +2015,6 @@ struct Engine {
   __device__ __forceinline__ void scale_rows() {
 #pragma unroll
     for (int k = 0; k < NVP; k++) Lrow[k] *= d_dinv;
-  }
-  // H <- H + sigma x x' on the dense factor (sigma = +-1; lane i holds x_i), LINPACK dchud / dchdd in the row-per-lane layout: step k
-  // broadcasts the pivot and x_k, every later row updates its column-k entry and its x.  Works on UNSCALED strictly-lower rows in
-  // Lrow and the diagonal in Lgg (the caller undoes scale_rows first and redoes it, with the LDS tile, after the last modification).
-  // Returns false if a down-date pivot lost more than two digits (r^2 <= 0.01 L_kk^2): the caller rebuilds.
-  __device__ __forceinline__ bool chol_rank1(real x, const real sigma, real& Lgg) {
-    int gq = g;
-    asm volatile("" : "+v"(gq));       // (opaque per call: see factor_core)
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < NVP; k++) {
-      const real Lkk = bc<G>(Lgg, k), xk = bc<G>(x, k);
-      const real l2 = Lkk * Lkk, r2 = m_fma(sigma * xk, xk, l2);
-      ok = ok && r2 > 0.01f * l2;
-      const real r = m_sqrt(m_max(r2, MINVALF)), iL = 1.f / Lkk, ic = Lkk / r;
-      const real c = r * iL, sn = xk * iL;
-      if (gq == k) Lgg = r;
-      if (gq > k) {
-        const real l = (Lrow[k] + sigma * sn * x) * ic;
-        Lrow[k] = l;
-        x = c * x - sn * l;
-      }
-    }
-    return ok;
   }
 
   // x <- (L L')^-1 x ; lane i holds x_i.  Lrow = the scaled rows (scale_rows), the LDS tile = the strictly lower part of L.
@@ -2522,11 +2238,7 @@ struct Engine {
     real alpha_prev = 0.f;
     unsigned long long set_prev = 0ull;
     int refine = 0;
-    const real gsm_norm = MM_NEWTON_GRADCHECK ? m_sqrt(gsum<G>(g < nv ? d_smooth * d_smooth : 0.f)) : 0.f;
-    (void)refine; (void)gsm_norm;
-#if MM_NEWTON_POLISH
-    bool polished = false;
-#endif
+    const real gsm_norm = m_sqrt(gsum<G>(g < nv ? d_smooth * d_smooth : 0.f));
     for (int iter = 0; iter < KD().iterations; iter++) {
       const bool on = r_active && r_jar < 0.f;
       const unsigned long long set_now = __ballot(on);
@@ -2540,17 +2252,10 @@ struct Engine {
         const int lane = threadIdx.x & 63;
         const unsigned long long gm = (G == 64 ? ~0ull : ((1ull << G) - 1ull)) << (lane - g);
         if (((set_now ^ set_prev) & gm) == 0ull) {
-#if MM_NEWTON_POLISH
-          if (polished) break;
-          polished = true;     // experiment: one more Newton step from the (nominally exact) minimiser
-#elif MM_NEWTON_GRADCHECK
           const real dm_ = g < nv ? Ma - d_smooth : 0.f;
           const real gref = m_sqrt(gsum<G>(dm_ * dm_));
           if (gn <= MM_GRAD_REL * gref + MM_GRAD_ABS * gsm_norm || refine >= MM_NEWTON_REFINE) break;
           refine++;            // the step was a full one on an unchanged set, yet the gradient is not down: refine from here
-#else
-          break;
-#endif
         }
       }
       set_prev = set_now;
@@ -2564,55 +2269,12 @@ struct Engine {
       // (M + diag(dadd)) search = -grad, so M search needs no product: the residual of the solve is of the order of the
       // rounding of an explicit product
       real Mv;
-      if constexpr (SP && !MM_NEWTON_TRUE_MV) Mv = g < nv ? -grad - dadd * search : 0.f;
+      if constexpr (SP) Mv = g < nv ? -grad - dadd * search : 0.f;
       else Mv = mul_m(search);
       real jv = r_sign * sh<G>(search, r_dof);
       real dm = Ma - d_smooth;
       real q1 = gsum<G>(search * dm), q2 = gsum<G>(0.5f * search * Mv);
       const real gtol = KD().tolerance * KD().ls_tolerance * sn / scale;
-#if MM_LS_DIRECT
-      // Exact line search in closed form (round 6).  phi'(alpha) = q1 + 2 q2 alpha + sum over the rows that are on at alpha of
-      // D_r jv_r (jar_r + alpha jv_r) is piecewise LINEAR and non-decreasing, with one break point per limit row, beta_r = -jar_r /
-      // jv_r.  Every lane evaluates phi' and its right-hand slope at ITS row's break point (lanes without one: at 0) by one sweep
-      // over the active rows of the group (broadcast of three words per row); the root lies on the linear piece that starts at the
-      // largest of these points where phi' <= 0:  alpha = beta - phi'(beta) / slope(beta+).  No iteration: the safeguarded Newton on
-      // phi' it replaces took 4...20 turns of two dependent group reductions each (n_ls 4...10 k cycles of a 112 k pass).
-      real alpha;
-      {
-        (void)gtol;
-        const real Aw = r_active ? r_jar : 1.f, Vw = r_active ? jv : 0.f, DVw = r_active ? r_D * jv : 0.f;
-        real beta = 0.f;
-        bool hasbp = false;
-        if (r_active && Vw != 0.f) {
-          const real b_ = -Aw / Vw;
-          if (b_ > 0.f && b_ < (real)1e30) { beta = b_; hasbp = true; }
-        }
-        real P = 0.f, S = 0.f;
-        unsigned long long m_ = __ballot(r_active);
-        if constexpr (G < 64) {
-#pragma unroll
-          for (int sft = G; sft < 64; sft <<= 1) m_ |= m_ >> sft;
-          m_ &= (1ull << G) - 1ull;
-        }
-        while (m_) {
-          const int j = __builtin_ctzll(m_);
-          m_ &= m_ - 1ull;
-          const real Aj = bc<G>(Aw, j), Vj = bc<G>(Vw, j), DVj = bc<G>(DVw, j);
-          const real x = m_fma(beta, Vj, Aj);
-          const bool self = hasbp && j == g;          // the lane's own row sits exactly on its break point: on beyond it iff jv < 0
-          const bool on = self ? (Vj < 0.f) : (x < 0.f);
-          const real t = on ? DVj : 0.f;
-          P = m_fma(t, self ? 0.f : x, P);
-          S = m_fma(t, Vj, S);
-        }
-        P += q1 + 2.f * beta * q2;
-        S += 2.f * q2;
-        const real key = (P <= 0.f) ? beta : -1.f;
-        const real kmax = gmax<G>(key);
-        const real cand = (key == kmax && kmax >= 0.f) ? beta - P / m_max(S, MINVALF) : 0.f;     // >= beta >= 0
-        alpha = gmax<G>(cand);
-      }
-#else
       // exact line search on the convex piecewise-quadratic phi(alpha): safeguarded Newton on phi'(alpha) = 0
       real alpha = 1.f, lo = 0.f, hi = -1.f;
       for (int it = 0; it < KD().ls_iterations; it++) {
@@ -2626,10 +2288,9 @@ struct Engine {
         real next = alpha - d1 / m_max(d2, MINVALF);
         if (hi >= 0.f && (next <= lo || next >= hi)) next = 0.5f * (lo + hi);
         else if (hi < 0.f && next <= lo) next = 2.f * lo + 1e-10f;
-        if (MM_LS_RELSTOP ? m_abs(next - alpha) <= MM_LS_RELSTOP_TOL * m_abs(alpha) : next == alpha) { alpha = next; break; }
+        if (next == alpha) { alpha = next; break; }
         alpha = next;
       }
-#endif
       if (!(alpha > 0.f)) break;
       d_qacc += alpha * search; Ma += alpha * Mv; r_jar += alpha * jv;
       alpha_prev = alpha;
@@ -3260,12 +2921,8 @@ struct Engine {
     PFN(PF_N_WARM, tn_);
     real alpha_prev = 0.f;
     unsigned long long set_prev = 0ull, sat_prev = 0ull;
-    unsigned long long set_fact = 0ull;     // the quadratic set the current factor was built for (incremental Newton)
-    bool have_fact = false;
-    (void)set_fact; (void)have_fact;
     int refine = 0;
-    const real gsm_norm = MM_NEWTON_GRADCHECK ? m_sqrt(gsum<G>(g < nv ? d_smooth * d_smooth : 0.f)) : 0.f;
-    (void)refine; (void)gsm_norm;
+    const real gsm_norm = m_sqrt(gsum<G>(g < nv ? d_smooth * d_smooth : 0.f));
     bool done = nefc == 0;     // envs of the wave that have no rows idle through the loop (wave-collective code below)
     for (int iter = 0; iter < KD().iterations; iter++) {
       bool on;
@@ -3280,14 +2937,10 @@ struct Engine {
         const int lane = threadIdx.x & 63;
         const unsigned long long gm = (G == 64 ? ~0ull : ((1ull << G) - 1ull)) << (lane - g);
         if ((((set_now ^ set_prev) | (sat_now ^ sat_prev)) & gm) == 0ull) {
-#if MM_NEWTON_GRADCHECK
           const real dm_ = g < nv ? Ma - d_smooth : 0.f;
           const real gref = m_sqrt(gsum<G>(dm_ * dm_));
           if (gn <= MM_GRAD_REL * gref + MM_GRAD_ABS * gsm_norm || refine >= MM_NEWTON_REFINE) done = true;
           else refine++;       // a full step on an unchanged set, yet the gradient is not down (ill-conditioned H): refine from here
-#else
-          done = true;
-#endif
         }
       }
 #if MM_NEWTON_TRACE
@@ -3296,46 +2949,9 @@ struct Engine {
       if (__ballot(!done) == 0ull) break;
       set_prev = set_now; sat_prev = sat_now;
       PFN(PF_N_GRAD, tn_);
-      bool rebuild = true;
-#if MM_NEWTON_INCR && !MM_F64
-      if constexpr (G == 64) {
-        // one env per wave: ballots are the env's row masks.  Rows that entered / left the quadratic set since the factor was built:
-        const unsigned long long ch = set_now ^ set_fact;
-        if (have_fact && refine == 0 && __popcll(ch) <= MM_NEWTON_INCR) {
-          real Lgg = g < NVP ? 1.f / d_dinv : 1.f;
-#pragma unroll
-          for (int k = 0; k < NVP; k++) Lrow[k] *= Lgg;           // undo scale_rows: unscaled strictly-lower rows
-          bool ok = true;
-          unsigned long long todo = ch;
-#pragma unroll
-          for (int q = 0; q < MM_NEWTON_INCR; q++) {        // straight-line copies: no loop-carried register state
-            if (todo) {
-              const int r = __builtin_ctzll(todo);
-              todo &= todo - 1ull;
-              const real sq = m_sqrt(bc<G>(r_D, r));
-              const real* Jr = W + KL().efcJ + r * RS;
-              const real x = g < nv ? sq * Jr[g] : 0.f;
-              ok = chol_rank1(x, ((set_now >> r) & 1ull) ? 1.f : -1.f, Lgg) && ok;
-            }
-          }
-          if (__ballot(!ok) == 0ull) {
-            if (g < NVP) {
-#pragma unroll
-              for (int k4 = 0; k4 < NVP / 4; k4++)
-                *reinterpret_cast<real4*>(W + o_tile + g * TD + 4 * k4) = make_real4(Lrow[4 * k4], Lrow[4 * k4 + 1], Lrow[4 * k4 + 2], Lrow[4 * k4 + 3]);
-              d_dinv = 1.f / Lgg;
-            } else d_dinv = 1.f;
-            GSYNC();
-            scale_rows();
-            rebuild = false;
-          }
-        }
-      }
-#endif
-      if (rebuild) {
       // H = M + J_A' D J_A
       real A[NVP];
-#if MM_MFMA_HBUILD && !MM_F64   /* fp64: the row-broadcast loop below (no f64 tile path) */
+#if !MM_F64   /* fp64: the row-broadcast loop below (no f64 tile path) */
       if constexpr (G == 64) {
         // One env per wave: the rank-nefc update J' D J is a (NVP x K)(K x NVP) product -- the one GEMM-shaped piece of the step
         // -- and goes through the matrix cores: v_mfma_f32_16x16x4_f32 (exact fp32 FMA chains, same peak rate as the vector
@@ -3353,109 +2969,56 @@ struct Engine {
         const int erows = KD().efc_rows;
         const int K4 = (nrows_wave + 3) >> 2;
         real* T = W + KL().u1;                   // the dense tile: the previous factor in there is dead
-        // one tile ROW (ti) at a time: NT - ti accumulator tiles live instead of NT (NT + 1) / 2 (12 instead of 24 VGPRs for the
-        // 36-dof leg, whose kernel sits at the 256-VGPR limit); the K sweep is repeated per tile row, its operand loads are cheap
-#ifndef MM_HBUILD_ONE_SWEEP
-#define MM_HBUILD_ONE_SWEEP 1
-#endif
-        if constexpr (MM_HBUILD_ONE_SWEEP != 0) {
-          // ONE K sweep with all NT (NT + 1) / 2 accumulator tiles.  Per K step the sweeps by tile row issued NT, NT - 1, ... matrix
-          // instructions behind one LDS round trip each -- all but the first are latency-bound (64 / 32 cycles of MFMA against a
-          // ~100-cycle round trip for a lone wave); one sweep issues the same instructions behind a single round trip.  (24
-          // accumulator VGPRs for the 48-wide tile of the 36-dof leg instead of 12: no new spills, leg +3.8 %.)
-          f4v acc[NT][NT];
+        // One K sweep with all NT (NT + 1) / 2 accumulator tiles: leg +3.8 % over a sweep per tile row, which issued NT, NT - 1, ...
+        // matrix instructions behind one LDS round trip each (24 accumulator VGPRs for the 36-dof leg instead of 12, no new spills).
+        // Software-pipelined by hand: the operands of step kb + 1 are requested before the MFMAs of step kb issue.  Clamped addresses
+        // + unconditional loads + a select: `ok ? table[i] : 0` compiles to a branch around the ds_read with a full s_waitcnt behind it.
+        f4v acc[NT][NT];
+#pragma unroll
+        for (int ti = 0; ti < NT; ti++)
+#pragma unroll
+          for (int tj = 0; tj < NT; tj++) acc[ti][tj] = f4v{0.f, 0.f, 0.f, 0.f};
+        auto fetch = [&](const int kb, real& dsc, real (&av)[NT]) __attribute__((always_inline)) {
+          const int row = 4 * kb + lk;
+          const bool rok = row < erows;
+          const int rr = rok ? row : 0;
+          const real* Jr = Jb + rr * RS;
+          const real dl = Dv[rr];
+#pragma unroll
+          for (int t = 0; t < NT; t++) {
+            const int col = 16 * t + lr;
+            const real v = Jr[col < NVP ? col : 0];
+            av[t] = (rok && col < NVP) ? v : 0.f;
+          }
+          dsc = rok ? dl : 0.f;
+        };
+        real dsc, av[NT];
+        fetch(0, dsc, av);
+        for (int kb = 0; kb < K4; kb++) {
+          real dsn, an[NT], bv[NT];
+          fetch(kb + 1, dsn, an);
+#pragma unroll
+          for (int t = 0; t < NT; t++) bv[t] = av[t] * dsc;
 #pragma unroll
           for (int ti = 0; ti < NT; ti++)
 #pragma unroll
-            for (int tj = 0; tj < NT; tj++) acc[ti][tj] = f4v{0.f, 0.f, 0.f, 0.f};
-          auto fetch = [&](const int kb, real& dsc, real (&av)[NT]) __attribute__((always_inline)) {
-            const int row = 4 * kb + lk;
-            const bool rok = row < erows;
-            const int rr = rok ? row : 0;
-            const real* Jr = Jb + rr * RS;
-            const real dl = Dv[rr];
+            for (int tj = ti; tj < NT; tj++) acc[ti][tj] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[ti], bv[tj], acc[ti][tj], 0, 0, 0);
+          dsc = dsn;
 #pragma unroll
-            for (int t = 0; t < NT; t++) {
-              const int col = 16 * t + lr;
-              const real v = Jr[col < NVP ? col : 0];
-              av[t] = (rok && col < NVP) ? v : 0.f;
-            }
-            dsc = rok ? dl : 0.f;
-          };
-          real dsc, av[NT];
-          fetch(0, dsc, av);
-          for (int kb = 0; kb < K4; kb++) {
-            real dsn, an[NT], bv[NT];
-            fetch(kb + 1, dsn, an);
+          for (int t = 0; t < NT; t++) av[t] = an[t];
+        }
 #pragma unroll
-            for (int t = 0; t < NT; t++) bv[t] = av[t] * dsc;
-#pragma unroll
-            for (int ti = 0; ti < NT; ti++)
-#pragma unroll
-              for (int tj = ti; tj < NT; tj++) acc[ti][tj] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[ti], bv[tj], acc[ti][tj], 0, 0, 0);
-            dsc = dsn;
-#pragma unroll
-            for (int t = 0; t < NT; t++) av[t] = an[t];
-          }
-#pragma unroll
-          for (int ti = 0; ti < NT; ti++)
-#pragma unroll
-            for (int tj = ti; tj < NT; tj++)
-#pragma unroll
-              for (int v = 0; v < 4; v++) {
-                const int i = 16 * ti + 4 * lk + v, j = 16 * tj + lr;
-                if (i < NVP && j < NVP) {
-                  T[i * TD + j] = acc[ti][tj][v];
-                  if (ti != tj) T[j * TD + i] = acc[ti][tj][v];
-                }
-              }
-        } else {
-#pragma unroll
-        for (int ti = 0; ti < NT; ti++) {
-          f4v acc[NT];
-#pragma unroll
-          for (int q = 0; q < NT; q++) acc[q] = f4v{0.f, 0.f, 0.f, 0.f};
-          // K sweep, software-pipelined by hand: the operands of step kb + 1 are requested before the MFMAs of step kb issue, so
-          // the LDS round trip (~100 cycles for a lone wave) hides behind the three 32-cycle matrix instructions instead of
-          // preceding them.  Clamped addresses + unconditional loads + a select: `ok ? table[i] : 0` compiles to a branch around
-          // the ds_read with a full s_waitcnt behind it.
-          auto fetch = [&](const int kb, real& dsc, real (&av)[NT]) __attribute__((always_inline)) {
-            const int row = 4 * kb + lk;
-            const bool rok = row < erows;
-            const int rr = rok ? row : 0;
-            const real* Jr = Jb + rr * RS;
-            const real dl = Dv[rr];
-#pragma unroll
-            for (int t = ti; t < NT; t++) {
-              const int col = 16 * t + lr;
-              const real v = Jr[col < NVP ? col : 0];
-              av[t] = (rok && col < NVP) ? v : 0.f;
-            }
-            dsc = rok ? dl : 0.f;
-          };
-          real dsc, av[NT];
-          fetch(0, dsc, av);
-          for (int kb = 0; kb < K4; kb++) {
-            real dsn, an[NT];
-            fetch(kb + 1, dsn, an);
-#pragma unroll
-            for (int tj = ti; tj < NT; tj++) acc[tj] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[ti], av[tj] * dsc, acc[tj], 0, 0, 0);
-            dsc = dsn;
-#pragma unroll
-            for (int t = ti; t < NT; t++) av[t] = an[t];
-          }
+        for (int ti = 0; ti < NT; ti++)
 #pragma unroll
           for (int tj = ti; tj < NT; tj++)
 #pragma unroll
             for (int v = 0; v < 4; v++) {
               const int i = 16 * ti + 4 * lk + v, j = 16 * tj + lr;
               if (i < NVP && j < NVP) {
-                T[i * TD + j] = acc[tj][v];
-                if (ti != tj) T[j * TD + i] = acc[tj][v];
+                T[i * TD + j] = acc[ti][tj][v];
+                if (ti != tj) T[j * TD + i] = acc[ti][tj][v];
               }
             }
-        }
-        }
         GSYNC();
         const int row = g < NVP ? g : 0;
 #pragma unroll
@@ -3492,8 +3055,6 @@ struct Engine {
       }
       PFN(PF_N_HBUILD, tn_);
       factor_core<false>(A);
-      }
-      set_fact = set_now; have_fact = true;
       PFN(PF_N_FACTOR, tn_);
       real search = -solve(grad);
       if (g >= nv || done) search = 0.f;
@@ -3526,7 +3087,7 @@ struct Engine {
             real next = alpha - d1 / m_max(d2, MINVALF);
             if (hi >= 0.f && (next <= lo || next >= hi)) next = 0.5f * (lo + hi);
             else if (hi < 0.f && next <= lo) next = 2.f * lo + 1e-10f;
-            if (MM_LS_RELSTOP ? m_abs(next - alpha) <= MM_LS_RELSTOP_TOL * m_abs(alpha) : next == alpha) lsdone = true;
+            if (next == alpha) lsdone = true;
             alpha = next;
           }
         }
@@ -3583,8 +3144,6 @@ struct Engine {
       }
       tw_signal(2, tw_n);
     }
-    constexpr bool SPG = GEN && MM_SPARSE_LDL && MM_SPARSE_GEN && NVP >= 8 && INTEG != 2;
-    const bool spg = SPG && (MM_SPARSE_GEN == 2 || KD().seg_nlevel > 0);   // general-row kernel on a model whose dof tree the sparse solve handles
     // MM_SKIP_QACCSM (round 6).  The unconstrained acceleration qacc_smooth = M^-1 qfrc_smooth enters the constrained solve in two
     // places only: as the alternative START of the Newton iteration (MuJoCo starts from whichever of qacc_warmstart and qacc_smooth
     // costs less) and inside the Gauss term of the cost, where it contributes a constant.  The cost is strictly convex: a solve that
@@ -3601,15 +3160,12 @@ struct Engine {
     const bool warm_ok = gor<G>(!(m_abs(d_warm) < 1e10f)) == 0;      // (lanes g >= nv hold 0)
     no_sm = MM_SKIP_QACCSM && !a.dbg && nefc > 0 && KD().iterations >= MM_SKIP_QACCSM_MIN_ITER && warm_ok;
     const bool wave_skip = __ballot(!no_sm) == 0ull;
-    if constexpr (!SP) { if (!spg && !wave_skip) PFT(PF_FACTOR, factor(0.f)); }
+    if constexpr (!SP) { if (!wave_skip) PFT(PF_FACTOR, factor(0.f)); }
     PFT(PF_ACT, passive_actuation());
     if (wave_skip) d_qaccsm = 0.f;     // the Gauss term's constant: never a value left over from an earlier pass
     else {
       if constexpr (SP) PFT(PF_SOLVE0, d_qaccsm = sp_factor_solve(0.f, d_smooth));
-      else {
-        if (spg) { if constexpr (SPG) PFT(PF_SOLVE0, d_qaccsm = spg_factor_solve(0.f, d_smooth)); }
-        else PFT(PF_SOLVE0, d_qaccsm = solve(d_smooth));
-      }
+      else PFT(PF_SOLVE0, d_qaccsm = solve(d_smooth));
     }
     PFT(PF_NEWTON, solve_constraints());
   }
@@ -3994,21 +3550,6 @@ __global__ void __launch_bounds__(MM_F64 ? 256 : 512) k_engine(KArgs a) {
     }
     __syncthreads();
   }
-  KConst kc;
-#if MM_CONST_IN_REGS
-  {
-    ConstWords hdr = reinterpret_cast<ConstWords>(reinterpret_cast<uintptr_t>(a.blob));
-    ConstWords cbw = reinterpret_cast<ConstWords>(reinterpret_cast<uintptr_t>(a.blob + a.cofs));
-    static_assert(sizeof(ConstBlock) == sizeof(Dims) + sizeof(Layout) + sizeof(Aux) && sizeof(ConstBlock) % 4 == 0, "ConstBlock is three packed word structs");
-    uint32_t* dst = reinterpret_cast<uint32_t*>(&kc);   // KConst starts with {Dims, Layout, Aux} = the ConstBlock
-#pragma unroll
-    for (int w_ = 0; w_ < (int)(sizeof(ConstBlock) / 4); w_++) dst[w_] = cbw[w_];
-#if MM_SEC_IN_REGS
-#pragma unroll
-    for (int s_ = 0; s_ < MM_NSEC; s_++) kc.sec[s_] = (int)hdr[MM_HEADER_WORDS + 2 * s_];
-#endif
-  }
-#endif
   int e = (blockIdx.x * wpb + wave) * EPW + lane / G;
   const int nenv = a.s.nenv;
   if ((blockIdx.x * wpb + wave) * EPW >= nenv) return;  // whole wave idle
@@ -4020,7 +3561,7 @@ __global__ void __launch_bounds__(MM_F64 ? 256 : 512) k_engine(KArgs a) {
   real* W = wsbase + (size_t)(wave * EPW + lane / G) * KL().total;
   const auto& L = KL();
   const auto& d = KD();
-  Engine<G, NVP, GEN, INTEG> E(a, kc, mb, W, g);
+  Engine<G, NVP, GEN, INTEG> E(a, mb, W, g);
   if (a.s.geom_size_env && a.s.geom_env_id >= 0) {
     E.env_has_gs = true;
     E.env_gsv[0] = a.s.geom_size_env[(size_t)e * 3]; E.env_gsv[1] = a.s.geom_size_env[(size_t)e * 3 + 1]; E.env_gsv[2] = a.s.geom_size_env[(size_t)e * 3 + 2];
@@ -4630,7 +4171,7 @@ __global__ void __launch_bounds__(MM_F64 ? 256 : 512) k_engine(KArgs a) {
       E.reinit_transients();
       GSYNC();
 #ifndef MM_REFOLD_CARRY
-#define MM_REFOLD_CARRY 0   /* 1: the reset-observation pass of a folded reset also writes a carry row (A/B switch) */
+#define MM_REFOLD_CARRY 0   /* 1: the reset-observation pass of a folded reset also writes a carry row; engine.py's FILE_FLAGS sets it for inst_D */
 #endif
       if (!MM_REFOLD_CARRY) E.carry_out = false;                 // (the row is voided at the state store)
       E.template run<MM_REFOLD_CARRY != 0>(0, true, time);

@@ -35,9 +35,6 @@
 #include "../../include/myosim.h"
 
 // (MINVALF, the floor of every guarded division, is defined per scalar type in myosim_engine_body.inc)
-#ifndef MM_MFMA_HBUILD
-#define MM_MFMA_HBUILD 1   /* Newton Hessian update J'DJ of one-env-per-wave kernels on the matrix cores (0: the row-broadcast loop) */
-#endif
 
 // ---- Philox4x32-10 (counter based; the oracle side reproduces it in numpy: oracle/env_oracle.py) -----------
 __device__ __host__ inline void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
@@ -97,15 +94,9 @@ struct Layout {
   int total;
 };
 
-#ifndef MM_FUSE_TENVEL
-/* 1: tendon velocities J qvel summed entry by entry inside tendon()'s Jacobian-entry sweep (one LDS float add per entry) instead of a pass
-   of their own with one lane per tendon.  Built and measured in round 6 (same-session A/B): hand 7.93 -> 7.70 M env-steps/s, leg 2.00 ->
-   1.96 M, self-contact hand 3.65 -> 3.60 M, elbow 32.9 -> 33.4 M -- gfx950 executes a ds_add_f32 at ~3 cycles per active lane, CU-wide
-   (tools/micro/lds_atomic_bench.hip), which costs more than the per-tendon walk it replaces.  OFF. */
-#define MM_FUSE_TENVEL 0
-#endif
 #ifndef MM_FOLD_RIGID_SEGMENTS
-#define MM_FOLD_RIGID_SEGMENTS 1   /* 0: A/B switch: every site-site segment of a tendon path is a path item of the kernel's sweep (rounds 1-5) */
+#define MM_FOLD_RIGID_SEGMENTS 1   /* 0: every site-site segment of a tendon path is a path item of the kernel's sweep (rounds 1-5) --
+                                      the reference path of paired accuracy comparisons */
 #endif
 // debug dump layout (tests only): one record per env in global memory
 struct DbgLayout {
@@ -127,7 +118,6 @@ struct Aux {
   int jnt_pack;          // per joint, 2 words: type | dofadr << 4 | qposadr << 14, bits(qpos0[qposadr]) -- one load instead of type -> address -> qpos0
   int body_chain;        // per body, 3 words: chain owned by the body's lane (its top body): bottom | level << 8 | children << 12, or -1; child chain tops, one byte each
   int ten_len0, ten_len0_f64;   // per tendon: the summed length of its path segments between rigidly connected bodies (folded at create): float table, double table
-  int jent_td;           // (MM_FUSE_TENVEL builds only) per tendon-Jacobian entry in processing order: tendon | dof << 16
 };
 
 // model constants the kernel reads through the scalar cache (appended to the device blob at KArgs::cofs, see KD / KL / KX)
@@ -185,35 +175,11 @@ typedef const __attribute__((address_space(4))) Aux ConstAux;
 typedef const __attribute__((address_space(4))) KArgs ConstKArgs;
 #define KA() (*(ConstKArgs*)(__builtin_amdgcn_kernarg_segment_ptr()))
 #define KCB_() (*reinterpret_cast<ConstBlockC*>(reinterpret_cast<uintptr_t>(a.blob + a.cofs)))
-// MM_CONST_IN_REGS = 1 (experiment, not the default): the ConstBlock and the section-offset table are read ONCE at kernel entry
-// into a by-value struct instead of through the scalar cache at every use (285 s_load per forward pass of the hand kernel,
-// SQ_INSTS_SMEM, each followed by an s_waitcnt lgkmcnt(0) that also drains the wave's LDS queue).  Measured on MI355X (A/B in
-// one session, tools/gpu_ab.sh): the ~150 extra long-lived wave-uniform values push SGPR spills from 324 to 478 lanes, the
-// two extra spill VGPRs tip the 241-VGPR hand kernel into 79 VGPR spills / 296 B scratch, and it LOSES: hand 4.63 -> 4.34 M,
-// reorient 2.08 -> 1.73 M env-steps/s, elbow unchanged (its time is dependent-latency, not scalar loads).  With only the
-// ConstBlock by value (MM_SEC_IN_REGS = 0): 38 VGPR spills, hand 4.56 M.  The scalar-cache path stays.
-#ifndef MM_CONST_IN_REGS
-#define MM_CONST_IN_REGS 0
-#endif
-struct KConst { Dims d; Layout L; Aux x; int sec[MM_NSEC]; };
-#ifndef MM_SEC_IN_REGS
-#define MM_SEC_IN_REGS 1
-#endif
-#if MM_CONST_IN_REGS
-#if MM_SEC_IN_REGS
-#define SECOFF_(S) (kc.sec[MM_SEC_##S])
-#else
-#define SECOFF_(S) SECOFF_G_(S)
-#endif
-#define KD() (kc.d)
-#define KL() (kc.L)
-#define KX() (kc.x)
-#else
+// model constants through the scalar cache at every use: all of them by value from kernel entry spilled and lost 7-17 % (NOTES.md)
 #define SECOFF_(S) SECOFF_G_(S)
 #define KD() (KCB_().d)
 #define KL() (KCB_().L)
 #define KX() (KCB_().x)
-#endif
 // A model table = (base of the model words, 32-bit word offset).  Element access builds the BYTE offset in 32 bits and adds it to
 // the base as an unsigned value: with the model read through L2 (LM = 0 kernels: `mb` is a uniform global pointer) that is the
 // `global_load v, v_off, s[base]` form -- one VGPR and one shift per load -- where indexing a `const T*` with an int index is a

@@ -66,7 +66,7 @@ SCHED_STRATEGY = {"default": "iterative-maxocc", "myosim_inst_E.hip": "iterative
 #  kernel where maxocc spills none at the same speed, 2.06 vs 2.06 M env-steps/s in one session; its SGPR spills, to VGPR lanes, go 217 -> 354)
 # Extra per-file flags.  -sink-insts-to-avoid-spills: hand pose <32,24> 5.55 -> 5.67 M; within +-1 % (mostly -) on the others.
 FILE_FLAGS = {"myosim_inst_B.hip": ["-mllvm", "-sink-insts-to-avoid-spills=1", "-mllvm", "-amdgpu-set-wave-priority=1"],   # wave priority: hand +0.6 %
-              # leg <64,36,GEN>: +0.8 %.  (Incremental Newton, -DMM_NEWTON_INCR=2 -- rank-one factor modifications when <= 2 rows changed set --
+              # leg <64,36,GEN>: +0.8 %.  (Incremental Newton -- rank-one factor modifications when <= 2 rows changed set, retired (NOTES.md) --
               # measured +2.4 % in the upright phase / +0.9 % in the steady mix of the episode, kernel 568 -> 559 us, for 52 spilled VGPRs and
               # 3x the HBM write traffic (4.0 -> 12.2 MB of scratch per launch): off.)
               "myosim_inst_H.hip": ["-mllvm", "-sink-insts-to-avoid-spills=1"],

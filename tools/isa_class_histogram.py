@@ -99,7 +99,7 @@ GROUPS = [  # function -> stage label of the stage timers (tools/gpu_perf.py)
                 "sd_box", "sd_cylinder", "sd_ellipsoid", "sd_shape", "seg_shape", "seg_shape_call", "seg_dg", "seg_bisect", "capsule_box_second",
                 "gscan_flag", "gscan_excl", "gsum_i", "Jrow")),
     ("vel", ("velocity_bias", "subtree_sum", "inert_mul", "cross_motion", "cross_force")), ("crb", ("crb", "sp_crb_entry")),
-    ("factor/solve", ("factor", "factor_core", "factor_solve", "scale_rows", "solve", "chol_rank1", "sp_factor_solve", "spg_factor_solve", "sp_solve_rows",
+    ("factor/solve", ("factor", "factor_core", "factor_solve", "scale_rows", "solve", "sp_factor_solve", "sp_solve_rows",
                       "sg_load_rows", "sg_pivots", "sg_anc_x", "sg_back", "sg_children", "sg_publish", "sg_path", "byte_of", "sp_dense_entry", "sp_dense_tile")),
     ("act", ("actuation", "passive_actuation", "smooth_force", "muscle_fl", "muscle_f0", "muscle_gain", "muscle_bias", "muscle_dynamics", "sigmoid5", "rows_to_dof")),
     ("newton", ("solve_constraints", "solve_constraints_gen", "cost_of", "cost_gen", "jac_mul", "jacT_mul", "row_force", "mul_m", "sp_mul_m")),

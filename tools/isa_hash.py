@@ -43,7 +43,7 @@ def main():
     out_path = sys.argv[1]
     args = sys.argv[2:]
     csrc = os.path.join(ROOT, "myosuite_amd", "csrc")
-    srcs = sorted(f for f in os.listdir(csrc) if f.startswith("myosim_inst_") and f.endswith(".hip"))
+    srcs = sorted(f for f in os.listdir(csrc) if (f.startswith("myosim_inst_") and f.endswith(".hip")) or f == "myosim_engine.hip")
     if args:
         srcs = [f for f in srcs if any(a in f for a in args)]
     os.makedirs("/tmp/isa", exist_ok=True)
