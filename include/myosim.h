@@ -61,9 +61,13 @@ enum { MM_INFO_NQ = 0, MM_INFO_NV, MM_INFO_NU, MM_INFO_NA, MM_INFO_NBODY, MM_INF
        MM_INFO_FOLDED_RESET,    /* 1: mm_rollout.autoreset is available for the WALK / REORIENT tasks on this model (64 lanes per env, a kernel of MM_KERNELS_OBS) */
        MM_INFO_FWD_CARRY,       /* 1: mm_task.fwd_carry is implemented for this model (see mm_task) */
        MM_INFO_TENDON_ITEMS,    /* tendon path items (site-site segments, wraps, fixed-tendon terms) the kernel sweeps per forward pass */
-       MM_INFO_TENDON_FOLDED }; /* path segments between two sites whose bodies no dof separates: constant length, summed into the tendon's
+       MM_INFO_TENDON_FOLDED,   /* path segments between two sites whose bodies no dof separates: constant length, summed into the tendon's
                                    constant at mm_model_create instead of being swept (a per-env mm_state.body_pos_env on a body such a
                                    segment spans is refused with MM_EUNSUPPORTED) */
+       MM_INFO_EFC_ROWS };      /* constraint rows allocated per env by the general-row kernels: njmax rounded up to 4 (0: limit rows only).
+                                   Up to 64 rows one per lane; 64 < njmax <= MM_MAX_EFC_ROWS two per lane of a wavefront (Euler, fp32,
+                                   one env per wave: no mm_task.fwd_carry, no folded reset, no "precision" mode); beyond: MM_EUNSUPPORTED */
+#define MM_MAX_EFC_ROWS 128
 
 /* ABI version of this header: bumped whenever a struct below gains / loses / reorders a field, an entry point changes its
  * signature or a status / enum value is renumbered.  A caller compares MM_ABI_VERSION (what it was built against) with
@@ -89,7 +93,7 @@ typedef struct {
                                     4 the solver hit its iteration cap, 8 contacts or constraint rows were dropped: contacts beyond
                                     mjModel.nconmax (in collider order), or constraint rows beyond njmax: equality, friction-loss and
                                     limit rows past it, and every contact whose rows do not all fit, while a later contact that
-                                    fits still gets rows, as in the oracle.  MuJoCo raises mjWARN_CONTACTFULL / mjWARN_CNSTRFULL
+                                    fits still gets rows, as in the oracle (njmax itself is at most MM_MAX_EFC_ROWS = 128).  MuJoCo raises mjWARN_CONTACTFULL / mjWARN_CNSTRFULL
                                     for the two; the oracle reports them as its warn bits 4 / 2, and tests map both onto this bit.
                                     16 a two-wave launch lost a partner wave (a bounded wait gave up: engine bug),
                                     32 a NaN / Inf / > 1e10 entry in the env's control vector: ALL its controls were set to 0 for this
@@ -300,7 +304,8 @@ int  mm_model_set_option(mm_model* m, const char* name, int value);
                         the mode that meets "state divergence vs CPU mj_step < 1e-4 rel over 1000 steps" on every env: MuJoCo's
                         mjtNum is double, and an fp32 state row alone already breaks the bound on ~1.5 % of the hand's envs.
    Available for limit-rows-only models (no contacts / equalities / friction loss) on the Euler integrator with nv <= 24 --
-   BASELINE.json's configs 2-3; MM_EUNSUPPORTED otherwise.  Model tables (the MYOB blob) are fp32 in every mode.  */
+   BASELINE.json's configs 2-3; MM_EUNSUPPORTED otherwise, and for every model with njmax > 64 (the two-rows-per-lane kernels are
+   fp32 only).  Model tables (the MYOB blob) are fp32 in every mode.  */
 enum { MM_PREC_F32 = 0, MM_PREC_F64 = 1, MM_PREC_F64_STATE = 2 };
 /* lanes per env a launch over `nenv` envs will use (the width is picked per launch from the batch size unless pinned
    with mm_model_set_lanes or fixed by the model's constraint tables) */

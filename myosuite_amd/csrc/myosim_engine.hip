@@ -9,6 +9,7 @@
 #include "myosim_inst_list.hpp"
 MM_KERNEL_LIST(MM_DECLARE)
 MM_KERNELS_OBS(MM_DECLARE_OBS)
+MM_KERNELS_S(MM_DECLARE_ROWS2)
 namespace mm64 {
 MM_KERNELS_F64(MM_DECLARE)
 }
@@ -185,6 +186,7 @@ struct mm_model {
   int lanes_auto = 1;        // pick the group width per launch from the batch size
   int lanes_user = 0;        // the width was pinned by the caller (mm_model_set_lanes), not chosen as the model's default
   int nvp = 24;
+  int rpl = 1;               // constraint rows per lane of the general-row kernels: 2 for 64 < njmax <= 128 (k_engine_rows2, 64 lanes per env)
   int waves_per_block = 0;   // 0 = auto
   int lds_model = 1;
   int blob_words = 0;
@@ -227,8 +229,10 @@ static const int kNvpChoices[] = {4, 24, 32, 36, 40};
 static int integ_kernel(int integrator) { return integrator == MM_INT_RK4 ? 1 : (integrator == MM_INT_IMPLICITFAST ? 2 : 0); }
 
 // is (lanes_per_env, padded nv, general-rows, integrator) a compiled instantiation?  (myosim_inst_list.hpp)
-static bool have_kernel(int G, int nvp, int gen, int rk4 = 0) {
+// rpl = 2: of the two-rows-per-lane kernels (MM_KERNELS_S)
+static bool have_kernel(int G, int nvp, int gen, int rk4 = 0, int rpl = 1) {
 #define X(G_, N_, GN_, RK_) if (G == G_ && nvp == N_ && gen == GN_ && rk4 == RK_) return true;
+  if (rpl == 2) { MM_KERNELS_S(X) return false; }
   MM_KERNEL_LIST(X)
 #undef X
   return false;
@@ -244,7 +248,8 @@ static bool have_kernel_f64(int G, int nvp, int gen, int rk4) {
 // the check every width decision goes through: a compiled instantiation of the model's kernel family
 static bool have_model_kernel(const mm_model* m, int G) {
   const int rk = integ_kernel(m->d.integrator);
-  return m->precision != MM_PREC_F32 ? have_kernel_f64(G, m->nvp, m->d.gen, rk) : have_kernel(G, m->nvp, m->d.gen, rk);
+  if (m->precision != MM_PREC_F32) return m->rpl == 1 && have_kernel_f64(G, m->nvp, m->d.gen, rk);
+  return have_kernel(G, m->nvp, m->d.gen, rk, m->rpl);
 }
 
 // LDS tables of one env.  two_wave: the layout of a launch that gives every env a helper wave (Engine::TW): tables that share words
@@ -278,7 +283,7 @@ static Layout env_layout(const mm_model* m, bool two_wave) {
   L.xvec = take(m->nvp);
   if (d.integrator == MM_INT_RK4) { L.rk_qpos0 = take(d.nq); L.rk_act0 = take(d.na); L.rk_adot = take(d.na); }
   if (d.integrator == MM_INT_IMPLICITFAST) { L.tenw = take(d.ntendon); L.dofw = take(d.nv); }
-  if (d.gen) { o = (o + 3) & ~3; L.efcJ = take(d.efc_rows * (m->nvp + 4)); L.rowtab = take(3 * m->lanes); }
+  if (d.gen) { o = (o + 3) & ~3; L.efcJ = take(d.efc_rows * (m->nvp + 4)); L.rowtab = take(3 * m->rpl * m->lanes); }
   if (two_wave) { o = (o + 3) & ~3; L.mtile = take(m->nvp * td + m->nvp); }
   // 16-byte aligned env stride (wide ds_read/ds_write never straddle), skewed by 4 words so that neighbouring
   // envs of a wave do not start on the same LDS bank
@@ -296,7 +301,7 @@ static Layout env_layout(const mm_model* m, bool two_wave) {
   return L;
 }
 static void build_layout(mm_model* m) {
-  m->d.efc_rows = std::min(m->lanes, (m->d.njmax + 3) & ~3);
+  m->d.efc_rows = std::min(m->rpl * m->lanes, (m->d.njmax + 3) & ~3);
   m->d.seg_u = 13 * m->nvp;
   const Dims& d = m->d;
   m->L = env_layout(m, false);
@@ -320,9 +325,10 @@ static int check_lanes(const mm_model* m, int lanes) {
   const Dims& d = m->d;
   if (lanes != 4 && lanes != 8 && lanes != 16 && lanes != 32 && lanes != 64) return 0;
   if (d.nbody > lanes || d.nv > lanes || d.njnt > lanes || m->nvp > lanes) return 0;
-  // one constraint row / equality per lane; the explicit pair list is swept in chunks of `lanes` pairs (make_constraint_gen), bounded
-  // by MM_MAX_PAIRS (the pair index shares a row-descriptor word with the row kind)
-  if (d.gen && (d.njmax > lanes || d.neq > lanes || d.npair > MM_MAX_PAIRS)) return 0;
+  // one constraint row (two with m->rpl = 2: one env per wave only) / one equality per lane; the explicit pair list is swept in chunks
+  // of `lanes` pairs (make_constraint_gen), bounded by MM_MAX_PAIRS (the pair index shares a row-descriptor word with the row kind)
+  if (d.gen && (d.njmax > m->rpl * lanes || d.neq > lanes || d.npair > MM_MAX_PAIRS)) return 0;
+  if (m->rpl == 2 && lanes != 64) return 0;
   return 1;
 }
 
@@ -857,7 +863,13 @@ extern "C" int mm_model_create(const uint32_t* blob, int nwords, mm_model** out)
   // default group width: the smallest that can own every body / dof / constraint row and has a compiled kernel
   m->lanes = 0;
   const int rk4 = integ_kernel(d.integrator);
-  for (int c : {4, 8, 16, 32, 64}) if (check_lanes(m, c) && have_kernel(c, m->nvp, d.gen, rk4)) { m->lanes = c; break; }
+  // more rows than a wavefront has lanes: two rows per lane, up to MM_MAX_EFC_ROWS (njmax <= 64 routes exactly as before)
+  if (d.gen && d.njmax > MM_MAX_EFC_ROWS) {
+    delete m;
+    return fail(MM_EUNSUPPORTED, "no compiled kernel owns this model (njmax > 128 constraint rows: the general-row kernels hold at most 128 rows per env, two per lane of a wavefront)");
+  }
+  m->rpl = (d.gen && d.njmax > 64) ? 2 : 1;
+  for (int c : {4, 8, 16, 32, 64}) if (check_lanes(m, c) && have_kernel(c, m->nvp, d.gen, rk4, m->rpl)) { m->lanes = c; break; }
   if (!m->lanes) {
     // a model whose rows need a wider group than its dofs do (torso: 18 dofs, 33 rows): take the next larger dense tile
     // that has a kernel at that width (the padding dofs are inert)
@@ -866,12 +878,13 @@ extern "C" int mm_model_create(const uint32_t* blob, int nwords, mm_model** out)
       for (int n : kNvpChoices) {
         if (n <= nvp_min) continue;
         m->nvp = n;
-        if (check_lanes(m, c) && have_kernel(c, n, d.gen, rk4)) { m->lanes = c; break; }
+        if (check_lanes(m, c) && have_kernel(c, n, d.gen, rk4, m->rpl)) { m->lanes = c; break; }
       }
       if (m->lanes) break;
     }
     if (!m->lanes) m->nvp = nvp_min;
   }
+  if (!m->lanes && m->rpl == 2) { delete m; return fail(MM_EUNSUPPORTED, "no compiled kernel owns this model (64 < njmax <= 128 takes the two-rows-per-lane kernels: Euler, nv <= 36, nbody / njnt / neq <= 64)"); }
   if (!m->lanes) { delete m; return fail(MM_EUNSUPPORTED, "no compiled kernel owns this model (needs > 64 lanes per env: nbody, nv, njnt or constraint rows > 64)"); }
   if (d.gen || rk4) m->lanes_auto = 0;   // row tables are sized for one group width; RK4 kernels exist for the default width only
   build_layout(m);
@@ -921,6 +934,7 @@ extern "C" int mm_model_set_option(mm_model* m, const char* name, int value) {
     // MM_PREC_F32 (default): the fp32 kernels.  MM_PREC_F64: fp64 arithmetic, registers and LDS tables; state rows stay fp32 (a
     // drop-in for every caller).  MM_PREC_F64_STATE: the four state rows of mm_state are fp64 as well.  (include/myosim.h)
     if (value != MM_PREC_F32 && value != MM_PREC_F64 && value != MM_PREC_F64_STATE) return fail(MM_EARG, "precision: MM_PREC_F32 / MM_PREC_F64 / MM_PREC_F64_STATE");
+    if (value != MM_PREC_F32 && m->rpl == 2) return fail(MM_EUNSUPPORTED, "precision: the two-rows-per-lane kernels (64 < njmax <= 128) are fp32 only");
     if (value != MM_PREC_F32) {
       bool any = false;
       for (int c : {4, 8, 16, 32, 64}) any = any || (check_lanes(m, c) && have_kernel_f64(c, m->nvp, m->d.gen, integ_kernel(m->d.integrator)));
@@ -953,7 +967,7 @@ static bool have_obs_kernel(int G, int nvp, int gen, int rk4);
 // mm_task.fwd_carry: the fp32 Euler kernels of 8 dofs and more (Engine::CARRY), and only where the action reaches nothing but act_dot
 // -- every actuator has activation dynamics
 static bool fwd_carry_ok(const mm_model* m) {
-  if (m->d.integrator == MM_INT_RK4 || m->precision != MM_PREC_F32 || m->d.nu == 0 || m->nvp < 8) return false;
+  if (m->d.integrator == MM_INT_RK4 || m->precision != MM_PREC_F32 || m->d.nu == 0 || m->nvp < 8 || m->rpl == 2) return false;
   const int32_t* dt = (const int32_t*)(m->h_blob.data() + m->sec[MM_SEC_ACT_DYNTYPE]);
   for (int u = 0; u < m->d.nu; u++) if (dt[u] == MM_DYN_NONE) return false;
   return true;
@@ -969,7 +983,8 @@ extern "C" int mm_model_info(const mm_model* m, int which) {
     case MM_INFO_NGEOM: return m->d.ngeom; case MM_INFO_WAVES_PER_BLOCK: return m->waves_per_block;
     case MM_INFO_MODEL_WORDS: return m->blob_words;
     case MM_INFO_BODY_CHAINS: return m->d.bchain_nlevel;
-    case MM_INFO_FOLDED_RESET: return (MM_FOLD_RESET && m->lanes == 64 && !m->lanes_auto && have_obs_kernel(64, m->nvp, m->d.gen, integ_kernel(m->d.integrator))) ? 1 : 0;
+    case MM_INFO_EFC_ROWS: return m->d.gen ? m->d.efc_rows : 0;
+    case MM_INFO_FOLDED_RESET: return (MM_FOLD_RESET && m->rpl == 1 && m->lanes == 64 && !m->lanes_auto && have_obs_kernel(64, m->nvp, m->d.gen, integ_kernel(m->d.integrator))) ? 1 : 0;
     case MM_INFO_FWD_CARRY: return fwd_carry_ok(m) ? 1 : 0;
     case MM_INFO_TENDON_ITEMS: return m->x.nitem;
     case MM_INFO_TENDON_FOLDED: return m->nfolded;
@@ -1038,6 +1053,23 @@ static int launch_f64_t(const mm_model* m, KArgs& a, dim3 grid, dim3 block, size
   if (g_info) return report_kernel(lm ? (const void*)mm64::k_engine<G, NVP, true, GEN, RK4> : (const void*)mm64::k_engine<G, NVP, false, GEN, RK4>, grid, block, lds, G, a.two_wave, lm);
   if (lm) hipLaunchKernelGGL((mm64::k_engine<G, NVP, true, GEN, RK4>), grid, block, lds, st, a);
   else hipLaunchKernelGGL((mm64::k_engine<G, NVP, false, GEN, RK4>), grid, block, lds, st, a);
+  HIPCHK(hipGetLastError());
+  return MM_OK;
+}
+
+// the two-rows-per-lane kernels (k_engine_rows2; MM_KERNELS_S)
+template <int NVP>
+static int launch_rows2_t(const mm_model* m, KArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t st, int lm) {
+  static std::atomic<unsigned> attr_done[2] = {{0u}, {0u}};
+  const unsigned bit = m->device < 32 ? (1u << m->device) : 0u;
+  if (!(attr_done[lm].load(std::memory_order_acquire) & bit) || !bit) {
+    if (lm) HIPCHK(hipFuncSetAttribute((const void*)k_engine_rows2<NVP, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    else HIPCHK(hipFuncSetAttribute((const void*)k_engine_rows2<NVP, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    attr_done[lm].fetch_or(bit, std::memory_order_release);
+  }
+  if (g_info) return report_kernel(lm ? (const void*)k_engine_rows2<NVP, true> : (const void*)k_engine_rows2<NVP, false>, grid, block, lds, 64, a.two_wave, lm);
+  if (lm) hipLaunchKernelGGL((k_engine_rows2<NVP, true>), grid, block, lds, st, a);
+  else hipLaunchKernelGGL((k_engine_rows2<NVP, false>), grid, block, lds, st, a);
   HIPCHK(hipGetLastError());
   return MM_OK;
 }
@@ -1134,11 +1166,12 @@ static int launch_on_device(const mm_model* m, KArgs& a, void* stream, const int
   int two_wave = (g_two_wave && integ_kernel(m->d.integrator) != 1 && want <= 4 && m->waves_per_block <= 0) ? 1 : 0;
   // precision-mode kernels: a lane's register state doubles, so they are built for one wave per SIMD (256-thread blocks, up to
   // 512 VGPRs + AGPRs per lane); no helper waves
+  if (m->rpl == 2) two_wave = 0;                // (no helper-wave form of the two-rows-per-lane kernels: Engine::TW)
   const bool f64 = m->precision != MM_PREC_F32;
   const int max_wpb = f64 ? 4 : 8;              // __launch_bounds__ of the family
   if (f64) { two_wave = 0; if (want > max_wpb) want = max_wpb; }
   // the reset-observation pass of a task (mm_task.obs_only) has its own kernel symbol where one is compiled (model through L2)
-  const bool obs_kernel = a.mode == 2 && a.t.obs_only && have_obs_kernel(G, m->nvp, m->d.gen, integ_kernel(m->d.integrator));
+  const bool obs_kernel = m->rpl == 1 && a.mode == 2 && a.t.obs_only && have_obs_kernel(G, m->nvp, m->d.gen, integ_kernel(m->d.integrator));
   int lm = 0, wpb = 0;
   size_t per_env = 0, model_bytes = 0;
   for (;;) {
@@ -1185,6 +1218,13 @@ static int launch_on_device(const mm_model* m, KArgs& a, void* stream, const int
     if (G == G_ && m->nvp == N_ && m->d.gen == GN_ && rk4 == RK_) return launch_obs_t<G_, N_, GN_ != 0, RK_>(m, a, grid, block, lds, st);
     MM_KERNELS_OBS(X)
 #undef X
+  }
+  if (m->rpl == 2) {
+#define X(G_, N_, GN_, RK_) \
+    if (G == G_ && m->nvp == N_ && m->d.gen == GN_ && rk4 == RK_) return launch_rows2_t<N_>(m, a, grid, block, lds, st, lm);
+    MM_KERNELS_S(X)
+#undef X
+    return fail(MM_EUNSUPPORTED, "no compiled two-rows-per-lane kernel for this (lanes_per_env, nv) combination");
   }
 #define X(G_, N_, GN_, RK_) \
   if (G == G_ && m->nvp == N_ && m->d.gen == GN_ && rk4 == RK_) return launch_t<G_, N_, GN_ != 0, RK_>(m, a, grid, block, lds, st, lm);
@@ -1236,6 +1276,7 @@ static int sized_copy(T* dst, const T* src, size_t min_size, const char* what) {
 static int check_task(const mm_model* m, const mm_state* s, const mm_task* t) {
   if (!m || !s || s->nenv <= 0 || !t) return fail(MM_EARG, "mm_env_step: bad argument");
   if (t->task == MM_TASK_POSE && !t->target_jnt_value) return fail(MM_EARG, "pose task needs target_jnt_value");
+  if (t->fwd_carry && m->rpl == 2) return fail(MM_EUNSUPPORTED, "mm_task.fwd_carry: not in the two-rows-per-lane kernels (64 < njmax <= 128; MM_INFO_FWD_CARRY reports 0)");
   if (t->fwd_carry && !fwd_carry_ok(m)) return fail(MM_EUNSUPPORTED, "mm_task.fwd_carry: Euler / implicitfast, fp32, nv >= 5, every actuator with activation dynamics (MM_INFO_FWD_CARRY)");
   if (t->task == MM_TASK_REACH && (!t->tip_sites || !t->target_pos || t->ntip <= 0)) return fail(MM_EARG, "reach task needs tip_sites/target_pos");
   if (t->task == MM_TASK_WALK) {
@@ -1294,6 +1335,7 @@ extern "C" int mm_rollout_step(const mm_model* m, const mm_state* s, const mm_ta
       if (r->target != t->target_jnt_value) return fail(MM_EARG, "mm_rollout_step: rollout.target must be the task's target_jnt_value buffer");
     } else if (t->task == MM_TASK_WALK || t->task == MM_TASK_REORIENT) {
       // the second (reset-observation) pass is decided per wavefront: one env per wave, general-row kernels
+      if (m->rpl == 2) return fail(MM_EUNSUPPORTED, "mm_rollout_step: no folded walk / reorient reset in the two-rows-per-lane kernels (64 < njmax <= 128; MM_INFO_FOLDED_RESET reports 0: reset through reset_mask instead)");
       if (!(pick_lanes(m, s->nenv) == 64 && have_obs_kernel(64, m->nvp, m->d.gen, integ_kernel(m->d.integrator))))
         return fail(MM_EUNSUPPORTED, "mm_rollout_step: the folded walk / reorient reset exists in the 64-lane kernels of MM_KERNELS_OBS (reset through reset_mask instead)");
       if (!r->episode || !t->step_count) return fail(MM_EARG, "mm_rollout_step: autoreset needs episode / step_count");

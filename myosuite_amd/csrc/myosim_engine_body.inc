@@ -721,8 +721,19 @@ struct SegLane {
 // All member functions are collective over the G lanes of one env group.  NVP = padded nv (compile time).
 // INTEG: 0 semi-implicit Euler (eulerdamp), 1 RK4, 2 implicitfast (compile-time variants: each one's state machine would cost
 // the others registers)
-template <int G, int NVP, bool GEN, int INTEG>
-struct Engine {
+// RPL: constraint rows per lane of the general-row pipeline.  1: lane r owns row r (an env holds at most G rows).  2: lane g owns rows
+// g and g + G (up to 128 rows at one env per wave) -- the second row's scalars live in RowHi; every one-row kernel has RPL = 1 and an
+// empty RowHi base.
+template <int RPL>
+struct RowHi {};
+template <>
+struct RowHi<2> {
+  bool r2_active, r2_eq;
+  real r2_D, r2_aref, r2_jar, r2_floss;
+};
+template <int G, int NVP, bool GEN, int INTEG, int RPL = 1>
+struct Engine : RowHi<RPL> {
+  static_assert(RPL == 1 || (RPL == 2 && GEN && G == 64 && INTEG == 0 && !MM_F64), "two rows per lane: the fp32 Euler general-row kernels at one env per wave");
   static constexpr bool RK4 = INTEG == 1, IMPL = INTEG == 2;
   // Two waves per env group (a.two_wave; the Euler kernels): when the batch leaves SIMDs empty -- leg-walk at 1024 envs is one
   // wave per SIMD, the elbow at 4096 envs half a wave, all of them waiting on dependent latency most of the time -- a second
@@ -731,7 +742,7 @@ struct Engine {
   // stage, CRB and factorisation, and -- dense kernels -- factorises M + h B for the Euler step while the main wave is in
   // Newton.  The two meet through LDS counters per env with bounded spin waits (a lost partner raises status bit 16
   // instead of hanging).
-  static constexpr bool TW = INTEG != 1;   // Euler and implicitfast (RK4's four forward passes per step would need the helper's pass logic)
+  static constexpr bool TW = INTEG != 1 && RPL == 1;   // Euler and implicitfast (RK4's four forward passes per step would need the helper's pass logic)
   static constexpr int TW_DONE = 0x7fffffff;
   int tw_n;     // forward passes opened so far (two-wave launches)
   int o_tile;   // LDS word offset of the dense tile factor_core / solve work on (u1; the helper wave's own tile in two-wave launches)
@@ -821,7 +832,7 @@ struct Engine {
   // of running the pipeline: 1 pass in (frame_skip + 1) saved, results bit-identical.
   // (not for the 4-wide kernels: the elbow's pass is 28 k cycles of latency next to a helper wave, and the hashes + the extra damped
   // solve of the trailing pass cost it more than the skipped pass saves: measured -2.5 %)
-  static constexpr bool CARRY = INTEG != 1 && !MM_F64 && NVP >= 8;      // Euler and implicitfast
+  static constexpr bool CARRY = INTEG != 1 && !MM_F64 && NVP >= 8 && RPL == 1;      // Euler and implicitfast
   // (two flags, not two row pointers: three 64-bit per-lane pointers held from the kernel's prologue to its state store were six
   //  VGPRs live across every stage -- exactly the 10...17 spilled VGPRs / 28...40 B of scratch of the 32-wide general-row kernel
   //  since round 4.  The row address is re-derived where it is used, from an env index made opaque there so that it is not hoisted
@@ -2833,6 +2844,109 @@ struct Engine {
       }
       r_eq = kind == MM_CON_EQUALITY;
     }
+    if constexpr (RPL == 2) row_owner_hi();
+  }
+
+  // RPL = 2: the owner stage of the lane's second row, g + G (the same arithmetic as the block above, on the RowHi scalars)
+  __device__ __forceinline__ void row_owner_hi() {
+    const auto& L = KL();
+    const real* RT = W + L.rowtab;
+    const int row = g + G;
+    this->r2_active = row < nefc; this->r2_eq = false; this->r2_D = 0.f; this->r2_aref = 0.f; this->r2_jar = 0.f; this->r2_floss = 0.f;
+    if (this->r2_active) {
+      const int desc = __float_as_int(RT[3 * row]), kind = desc & 7, id = desc >> 3;
+      const real x = RT[3 * row + 1], dA = RT[3 * row + 2];
+      real vel = 0.f;
+      {
+        const real4* J4 = reinterpret_cast<const real4*>(Jrow(row));
+        const int nv_ = KD().nv;
+#pragma unroll
+        for (int k4 = 0; k4 < NVP / 4; k4++) {
+          const real4 j4 = J4[k4];
+          const real* qv = W + L.qvel + 4 * k4;
+          const real q0 = qv[0], q1 = qv[1], q2 = qv[2], q3 = qv[3];
+          vel += (4 * k4 < nv_ ? j4.x * q0 : 0.f) + (4 * k4 + 1 < nv_ ? j4.y * q1 : 0.f) + (4 * k4 + 2 < nv_ ? j4.z * q2 : 0.f) +
+                 (4 * k4 + 3 < nv_ ? j4.w * q3 : 0.f);
+        }
+      }
+      const float *si, *sr;
+      if (kind == MM_CON_EQUALITY) { si = MF_(EQ_SOLIMP) + 5 * id; sr = MF_(EQ_SOLREF) + 2 * id; }
+      else if (kind == MM_CON_LIMIT_JOINT) { si = MF_(JNT_SOLIMP) + 5 * id; sr = MF_(JNT_SOLREF) + 2 * id; }
+      else if (kind == MM_CON_LIMIT_TENDON) { si = MF_(TENDON_SOLIMP) + 5 * id; sr = MF_(TENDON_SOLREF) + 2 * id; }
+      else if (kind == MM_CON_FRICTION_DOF) { si = MF_(DOF_SOLIMP) + 5 * id; sr = MF_(DOF_SOLREF) + 2 * id; this->r2_floss = MF_(DOF_FRICTIONLOSS)[id]; }
+      else { si = MF_(PAIR_SOLIMP) + 5 * id; sr = MF_(PAIR_SOLREF) + 2 * id; }
+      impedance(si, sr, x, dA, vel, this->r2_D, this->r2_aref);
+      if (kind == MM_CON_CONTACT && MI_(PAIR_CONDIM)[id] > 1) {
+        const real m_ = MF_(PAIR_FRICTION)[3 * id];
+        this->r2_D = 1.f / m_max(MINVALF, 2.f * m_ * m_ / this->r2_D);
+      }
+      this->r2_eq = kind == MM_CON_EQUALITY;
+    }
+  }
+  // RPL = 2: J x for both rows of the lane (rows g and g + G share the operand vector)
+  __device__ __forceinline__ real jac_mul2(real x, real& s_hi) const {
+    const real4* J = reinterpret_cast<const real4*>(Jrow(g));
+    const real4* Jh = reinterpret_cast<const real4*>(Jrow(g + G));
+    real s = 0.f, h = 0.f;
+    if constexpr (LDS_VECTOR) {
+      real* X = W + KL().xvec;
+      if (g < NVP) X[g] = x;
+      GSYNC();          // (not optional: see jac_mul)
+#pragma unroll
+      for (int k = 0; k < NVP / 4; k++) {
+        const real4 j4 = J[k], h4 = Jh[k], x4 = *reinterpret_cast<const real4*>(X + 4 * k);
+        s += j4.x * x4.x + j4.y * x4.y + j4.z * x4.z + j4.w * x4.w;
+        h += h4.x * x4.x + h4.y * x4.y + h4.z * x4.z + h4.w * x4.w;
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < NVP / 4; k++) {
+        const real4 j4 = J[k], h4 = Jh[k];
+        const real x0 = bc<G>(x, 4 * k), x1 = bc<G>(x, 4 * k + 1), x2 = bc<G>(x, 4 * k + 2), x3 = bc<G>(x, 4 * k + 3);
+        s += j4.x * x0 + j4.y * x1 + j4.z * x2 + j4.w * x3;
+        h += h4.x * x0 + h4.y * x1 + h4.z * x2 + h4.w * x3;
+      }
+    }
+    s_hi = h;
+    return s;
+  }
+  // RPL = 2: J' f with the forces of rows 0 .. G - 1 in f and of rows G .. 2 G - 1 in f_hi (lane r - G); the loop of jacT_mul, the
+  // source register picked per turn (wave-uniform: a turn of four rows never straddles row G)
+  __device__ __forceinline__ real jacT_mul2(real f, real f_hi) const {
+    const real* Jc = W + KL().efcJ + (g < NVP ? g : 0);
+    real s = 0.f;
+    real j0 = Jc[0], j1 = Jc[RS], j2 = Jc[2 * RS], j3 = Jc[3 * RS];
+    for (int r = 0; r < nrows_wave; r += 4) {
+      const int rn = r + 4 < nrows_wave ? r + 4 : r;
+      const real n0 = Jc[rn * RS], n1 = Jc[(rn + 1) * RS], n2 = Jc[(rn + 2) * RS], n3 = Jc[(rn + 3) * RS];
+      const real fr = r < G ? f : f_hi;
+      const int rl_ = r & (G - 1);
+      s += j0 * bc<G>(fr, rl_) + j1 * bc<G>(fr, rl_ + 1) + j2 * bc<G>(fr, rl_ + 2) + j3 * bc<G>(fr, rl_ + 3);
+      j0 = n0; j1 = n1; j2 = n2; j3 = n3;
+    }
+    return g < KD().nv ? s : 0.f;
+  }
+  // RPL = 2: row_force on the scalars of the lane's second row
+  __device__ __forceinline__ real row_force_hi(real x, bool& quad) const {
+    const real f = -this->r2_D * x;
+    const bool fr = this->r2_floss > 0.f;
+    quad = this->r2_active && (fr ? m_abs(f) < this->r2_floss : (this->r2_eq || x < 0.f));
+    const real v = fr ? clampf(f, -this->r2_floss, this->r2_floss) : (quad ? f : 0.f);
+    return this->r2_active ? v : 0.f;
+  }
+  __device__ __forceinline__ real cost_gen2(real x, real Ma) {
+    real c = 0.5f * (x - d_qaccsm) * (Ma - d_smooth);
+    real jh;
+    r_jar = jac_mul2(x, jh) - r_aref;
+    this->r2_jar = jh - this->r2_aref;
+    bool quad;
+    (void)row_force(r_jar, quad);
+    if (quad) c += 0.5f * r_D * r_jar * r_jar;
+    else if (r_floss > 0.f && r_active) c += r_floss * (m_abs(r_jar) - 0.5f * r_floss / r_D);
+    (void)row_force_hi(this->r2_jar, quad);
+    if (quad) c += 0.5f * this->r2_D * this->r2_jar * this->r2_jar;
+    else if (this->r2_floss > 0.f && this->r2_active) c += this->r2_floss * (m_abs(this->r2_jar) - 0.5f * this->r2_floss / this->r2_D);
+    return gsum<G>(c);
   }
 
   // (J x)_r for the row owned by this lane; x lives in the dof lanes
@@ -2902,6 +3016,7 @@ struct Engine {
   }
 
   __device__ __forceinline__ void solve_constraints_gen() {
+    if constexpr (RPL == 2) { solve_constraints_gen2(); return; }
     const int nv = KD().nv;
     niter = 0;
     d_qfrccon = 0.f;
@@ -3111,6 +3226,191 @@ struct Engine {
     }
     bool on2;
     d_qfrccon = jacT_mul(row_force(r_jar, on2));
+    PFN(PF_N_GRAD, tn_);
+#undef PFN
+  }
+
+  // RPL = 2: the Newton solve of solve_constraints_gen with two rows per lane -- the same iteration, exits and line search; every
+  // per-row quantity (force, active-set signature, line-search terms, the running J a - aref) exists twice, once per owned row, and
+  // the D vector of the MFMA Hessian build has 2 G entries.  One env per wave, fp32 (Engine's static_assert).
+  __device__ __forceinline__ void solve_constraints_gen2() {
+    const int nv = KD().nv;
+    niter = 0;
+    d_qfrccon = 0.f;
+    if (nrows_wave == 0) { d_qacc = d_qaccsm; return; }
+    const real scale = 1.f / (KD().meaninertia * (real)(nv > 1 ? nv : 1));
+#define PFN(stage, t0_) do { MM_FENCE(); if (MM_STAGE_PROF && !MM_KIN_PROF && a.prof) { const unsigned long long t1_ = clock64(); pf[MM_STAGE_PROF ? stage : 0] += t1_ - t0_; t0_ = t1_; } } while (0)
+    unsigned long long tn_ = (MM_STAGE_PROF && a.prof) ? clock64() : 0;
+    real Ma_ws = mul_m(d_warm);
+    real cost_ws = cost_gen2(d_warm, Ma_ws);     // (also latches both r_jar at the warm start)
+    real Ma;
+    if (no_sm) { d_qacc = d_warm; Ma = Ma_ws; }
+    else {
+      real cost_sm = cost_gen2(d_qaccsm, d_smooth);
+      if (cost_ws < cost_sm) { d_qacc = d_warm; Ma = Ma_ws; (void)cost_gen2(d_qacc, Ma); }
+      else { d_qacc = d_qaccsm; Ma = d_smooth; }
+    }
+    PFN(PF_N_WARM, tn_);
+    real alpha_prev = 0.f;
+    unsigned long long set_prev = 0ull, sat_prev = 0ull, set_prev_h = 0ull, sat_prev_h = 0ull;
+    int refine = 0;
+    const real gsm_norm = m_sqrt(gsum<G>(g < nv ? d_smooth * d_smooth : 0.f));
+    bool done = nefc == 0;
+    for (int iter = 0; iter < KD().iterations; iter++) {
+      bool on, on_h;
+      const real rf = row_force(r_jar, on), rf_h = row_force_hi(this->r2_jar, on_h);
+      const unsigned long long set_now = __ballot(on), sat_now = KD().nfric ? __ballot(rf > 0.f && !on) : 0ull;
+      const unsigned long long set_now_h = __ballot(on_h), sat_now_h = KD().nfric ? __ballot(rf_h > 0.f && !on_h) : 0ull;
+      d_qfrccon = jacT_mul2(rf, rf_h);
+      real grad = g < nv ? Ma - d_smooth - d_qfrccon : 0.f;
+      real gn = m_sqrt(gsum<G>(grad * grad));
+      if (scale * gn < KD().tolerance) done = true;
+      if (!done && iter > 0 && m_abs(alpha_prev - 1.f) < 1e-3f) {
+        if (((set_now ^ set_prev) | (sat_now ^ sat_prev) | (set_now_h ^ set_prev_h) | (sat_now_h ^ sat_prev_h)) == 0ull) {
+          const real dm_ = g < nv ? Ma - d_smooth : 0.f;
+          const real gref = m_sqrt(gsum<G>(dm_ * dm_));
+          if (gn <= MM_GRAD_REL * gref + MM_GRAD_ABS * gsm_norm || refine >= MM_NEWTON_REFINE) done = true;
+          else refine++;
+        }
+      }
+      if (__ballot(!done) == 0ull) break;
+      set_prev = set_now; sat_prev = sat_now; set_prev_h = set_now_h; sat_prev_h = sat_now_h;
+      PFN(PF_N_GRAD, tn_);
+      // H = M + J_A' D J_A through the matrix cores (solve_constraints_gen: the same sweep over up to 2 G rows)
+      real A[NVP];
+      {
+        constexpr int NT = (NVP + 15) / 16;
+        typedef real f4v __attribute__((ext_vector_type(4)));
+        real* Dv = W + KL().rowtab;              // row table of make_constraint (3 x 2 G words): dead since the owner stage
+        Dv[g] = on ? r_D : 0.f;
+        Dv[g + G] = on_h ? this->r2_D : 0.f;
+        GSYNC();
+        const int lr = g & 15, lk = g >> 4;
+        const real* Jb = W + KL().efcJ;
+        const int erows = KD().efc_rows;
+        const int K4 = (nrows_wave + 3) >> 2;
+        real* T = W + KL().u1;
+        f4v acc[NT][NT];
+#pragma unroll
+        for (int ti = 0; ti < NT; ti++)
+#pragma unroll
+          for (int tj = 0; tj < NT; tj++) acc[ti][tj] = f4v{0.f, 0.f, 0.f, 0.f};
+        auto fetch = [&](const int kb, real& dsc, real (&av)[NT]) __attribute__((always_inline)) {
+          const int row = 4 * kb + lk;
+          const bool rok = row < erows;
+          const int rr = rok ? row : 0;
+          const real* Jr = Jb + rr * RS;
+          const real dl = Dv[rr];
+#pragma unroll
+          for (int t = 0; t < NT; t++) {
+            const int col = 16 * t + lr;
+            const real v = Jr[col < NVP ? col : 0];
+            av[t] = (rok && col < NVP) ? v : 0.f;
+          }
+          dsc = rok ? dl : 0.f;
+        };
+        real dsc, av[NT];
+        fetch(0, dsc, av);
+        for (int kb = 0; kb < K4; kb++) {
+          real dsn, an[NT], bv[NT];
+          fetch(kb + 1, dsn, an);
+#pragma unroll
+          for (int t = 0; t < NT; t++) bv[t] = av[t] * dsc;
+#pragma unroll
+          for (int ti = 0; ti < NT; ti++)
+#pragma unroll
+            for (int tj = ti; tj < NT; tj++) acc[ti][tj] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[ti], bv[tj], acc[ti][tj], 0, 0, 0);
+          dsc = dsn;
+#pragma unroll
+          for (int t = 0; t < NT; t++) av[t] = an[t];
+        }
+#pragma unroll
+        for (int ti = 0; ti < NT; ti++)
+#pragma unroll
+          for (int tj = ti; tj < NT; tj++)
+#pragma unroll
+            for (int v = 0; v < 4; v++) {
+              const int i = 16 * ti + 4 * lk + v, j = 16 * tj + lr;
+              if (i < NVP && j < NVP) {
+                T[i * TD + j] = acc[ti][tj][v];
+                if (ti != tj) T[j * TD + i] = acc[ti][tj][v];
+              }
+            }
+        GSYNC();
+        const int row = g < NVP ? g : 0;
+#pragma unroll
+        for (int k4 = 0; k4 < NVP / 4; k4++) {
+          const real4 r = *reinterpret_cast<const real4*>(T + row * TD + 4 * k4);
+          A[4 * k4] = Mrow[4 * k4] + r.x; A[4 * k4 + 1] = Mrow[4 * k4 + 1] + r.y;
+          A[4 * k4 + 2] = Mrow[4 * k4 + 2] + r.z; A[4 * k4 + 3] = Mrow[4 * k4 + 3] + r.w;
+        }
+        if (g >= NVP) {
+#pragma unroll
+          for (int k = 0; k < NVP; k++) A[k] = 0.f;
+        }
+        GSYNC();                                  // the factor below rewrites the tile
+      }
+      PFN(PF_N_HBUILD, tn_);
+      factor_core<false>(A);
+      PFN(PF_N_FACTOR, tn_);
+      real search = -solve(grad);
+      if (g >= nv || done) search = 0.f;
+      PFN(PF_N_SOLVE, tn_);
+      real sn = m_sqrt(gsum<G>(search * search));
+      if (sn < MINVALF) done = true;
+      real Mv = mul_m(search);
+      real jv_h;
+      real jv = jac_mul2(search, jv_h);
+      PFN(PF_N_PROD, tn_);
+      real dm = Ma - d_smooth;
+      real q1 = gsum<G>(search * dm), q2 = gsum<G>(0.5f * search * Mv);
+      const real gtol = KD().tolerance * KD().ls_tolerance * sn / scale;
+      real alpha = 1.f, lo = 0.f, hi = -1.f;
+      bool lsdone = done;
+      for (int it = 0; it < KD().ls_iterations; it++) {
+        real d1 = 0.f, d2 = 0.f;
+        {
+          bool q;
+          const real x = r_jar + alpha * jv;
+          const real f = row_force(x, q);
+          d1 = -f * jv;
+          if (q) d2 = r_D * jv * jv;
+          const real xh = this->r2_jar + alpha * jv_h;
+          const real fh = row_force_hi(xh, q);
+          d1 -= fh * jv_h;
+          if (q) d2 += this->r2_D * jv_h * jv_h;
+        }
+        d1 = gsum<G>(d1) + q1 + 2.f * alpha * q2;
+        d2 = gsum<G>(d2) + 2.f * q2;
+        if (!lsdone) {
+          if (m_abs(d1) < m_max(gtol, MM_LS_DTOL * m_abs(q1))) lsdone = true;
+          else {
+            if (d1 < 0.f) lo = alpha; else hi = alpha;
+            real next = alpha - d1 / m_max(d2, MINVALF);
+            if (hi >= 0.f && (next <= lo || next >= hi)) next = 0.5f * (lo + hi);
+            else if (hi < 0.f && next <= lo) next = 2.f * lo + 1e-10f;
+            if (next == alpha) lsdone = true;
+            alpha = next;
+          }
+        }
+        if (__ballot(!lsdone) == 0ull) break;
+      }
+      if (!(alpha > 0.f)) done = true;
+      if (!done) {
+        d_qacc += alpha * search; Ma += alpha * Mv; r_jar += alpha * jv; this->r2_jar += alpha * jv_h;
+        alpha_prev = alpha;
+        niter = iter + 1;
+      }
+      {
+        real stepmax = gmax<G>(m_abs(alpha * search)), qmax = gmax<G>(m_abs(d_qacc));
+        if (!done && stepmax <= MM_STEP_RES * m_max(qmax, 1.f)) done = true;
+      }
+      if (iter == KD().iterations - 1 && !done) status |= 4;
+      PFN(PF_N_LS, tn_);
+    }
+    bool on2, on2_h;
+    const real rfe = row_force(r_jar, on2), rfe_h = row_force_hi(this->r2_jar, on2_h);
+    d_qfrccon = jacT_mul2(rfe, rfe_h);
     PFN(PF_N_GRAD, tn_);
 #undef PFN
   }
@@ -3500,729 +3800,21 @@ struct Engine {
 #define ST_LD(p, i) ((p)[i])
 #define ST_ST(p, i, v) ((p)[i] = (v))
 #endif
+// The kernel body is myosim_engine_kernel_body.inc, included once per kernel symbol: k_engine (RPL = 1: one constraint row per lane --
+// every kernel of MM_KERNEL_LIST / _OBS / _F64) and k_engine_rows2 (RPL = 2).  Included text rather than a shared device function: that
+// keeps the code of k_engine's instantiations what it was before the second symbol existed (tools/kernel_table.py).
 template <int G, int NVP, bool LM, bool GEN, int INTEG, bool OBS = false>
 __global__ void __launch_bounds__(MM_F64 ? 256 : 512) k_engine(KArgs a) {
-#if MM_F64
-  extern __shared__ __attribute__((aligned(16))) double lds_f64[];
-  real* const lds = lds_f64;
-#else
-  extern __shared__ real lds[];
-#endif
-  constexpr int EPW = 64 / G;  // envs per wave
-  const int lane = threadIdx.x & 63;
-  // two-wave launches (Engine::TW): waves [0, wpb) are the main waves of the block's envs, waves [wpb, 2 wpb) their helpers
-  const bool two_wave = Engine<G, NVP, GEN, INTEG>::TW && a.two_wave;
-  const int wpb = two_wave ? (blockDim.x >> 7) : (blockDim.x >> 6);
-  const bool helper = two_wave && (int)(threadIdx.x >> 6) >= wpb;
-  const int wave = (int)(threadIdx.x >> 6) - (helper ? wpb : 0);
-  const int g = lane % G;
-  unsigned long long t_start = (MM_STAGE_PROF && a.prof) ? clock64() : 0;
-  // reset-observation pass (mm_task.obs_only with an env mask): a block none of whose envs is flagged leaves before the model
-  // is staged -- every wave scans the block's whole env range, so the decision is block-uniform and nobody is left waiting at
-  // the barrier (the pass is launched after every step of the non-Pose tasks and usually has nothing to do)
-  if (a.mode == 2 && (OBS || KA().t.obs_only) && KA().t.env_mask) {
-    const int epb = wpb * EPW, e0 = blockIdx.x * epb;
-    bool any = false;
-    for (int i = lane; i < epb; i += 64) any |= (e0 + i < a.s.nenv) && KA().t.env_mask[e0 + i] != 0;
-    if (__ballot(any) == 0ull) return;
-  }
-  // ---- stage the model tables into LDS once per block (all waves participate)
-  const uint32_t* mb = a.blob;
-  real* wsbase = lds;
-  if (LM) {
-    uint32_t* lm = reinterpret_cast<uint32_t*>(lds);
-    // 128-bit copies, four in flight per thread (word by word this was one serialised HBM / L2 round trip per 2 KB of model: 16-22
-    // of them, ~1 % of the launch)
-    const uint4* src4 = reinterpret_cast<const uint4*>(a.blob);
-    uint4* dst4 = reinterpret_cast<uint4*>(lm);
-    const int n4 = a.blob_words >> 2;
-#pragma unroll 4
-    for (int i = threadIdx.x; i < n4; i += blockDim.x) dst4[i] = src4[i];
-    for (int i = (n4 << 2) + threadIdx.x; i < a.blob_words; i += blockDim.x) lm[i] = a.blob[i];
-    __syncthreads();
-    mb = lm;
-    wsbase = reinterpret_cast<real*>(lm + ((a.blob_words + 3) & ~3));   // (the model copy is 32-bit words whatever `real` is)
-  }
-  if (two_wave) {   // the meeting counters of the block's envs start at zero
-    if ((int)threadIdx.x < wpb * EPW) {
-      real* Wf = wsbase + (size_t)threadIdx.x * KL().total + KL().flags;
-      reinterpret_cast<int*>(Wf)[0] = 0; reinterpret_cast<int*>(Wf)[1] = 0; reinterpret_cast<int*>(Wf)[2] = 0; reinterpret_cast<int*>(Wf)[3] = 0;
-    }
-    __syncthreads();
-  }
-  int e = (blockIdx.x * wpb + wave) * EPW + lane / G;
-  const int nenv = a.s.nenv;
-  if ((blockIdx.x * wpb + wave) * EPW >= nenv) return;  // whole wave idle
-  bool dup = e >= nenv;
-  if (dup) e = nenv - 1;  // surplus groups recompute the last env (they never store)
-  if (a.mode == 2 && KA().t.env_mask && !KA().t.env_mask[e]) dup = true;   // masked-out envs are left untouched
-  bool obs_only = OBS || (a.mode == 2 && KA().t.obs_only);
-  if (obs_only && __ballot(!dup) == 0ull) return;   // reset-observation pass: waves without a reset env do nothing
-  real* W = wsbase + (size_t)(wave * EPW + lane / G) * KL().total;
-  const auto& L = KL();
-  const auto& d = KD();
-  Engine<G, NVP, GEN, INTEG> E(a, mb, W, g);
-  if (a.s.geom_size_env && a.s.geom_env_id >= 0) {
-    E.env_has_gs = true;
-    E.env_gsv[0] = a.s.geom_size_env[(size_t)e * 3]; E.env_gsv[1] = a.s.geom_size_env[(size_t)e * 3 + 1]; E.env_gsv[2] = a.s.geom_size_env[(size_t)e * 3 + 2];
-  }
-  if (a.s.geom_type_env && a.s.geom_env_id >= 0) E.env_gtype = a.s.geom_type_env[e];
-  E.env = e;
-  if constexpr (Engine<G, NVP, GEN, INTEG>::TW) {
-    if (helper) {                               // everything it needs and leaves lives in the env's LDS tables
-      E.helper_loop();
-      if (MM_STAGE_PROF && a.prof && blockIdx.x == 0 && wave == 0 && lane == 0) {      // tools build: the helper wave's own timers
-        E.pf[MM_STAGE_PROF ? PF_TOTAL : 0] = clock64() - t_start;
-#pragma unroll
-        for (int i = 0; i < (MM_STAGE_PROF ? NPROF : 1); i++) a.prof[(MM_STAGE_PROF ? NPROF : 1) + i] = E.pf[i];
-      }
-      return;
-    }
-  }
-
-  // ---- load state (HBM -> LDS tables / owner registers)
-  for (int i = g; i < d.nq; i += G) W[L.qpos + i] = ST_LD(a.s.qpos, (size_t)e * d.nq + i);
-  if (g < d.nv) {
-    E.d_qvel = ST_LD(a.s.qvel, (size_t)e * d.nv + g);
-    E.d_warm = ST_LD(a.s.qacc_warmstart, (size_t)e * d.nv + g);
-    W[L.qvel + g] = E.d_qvel;
-  }
-  for (int i = g; i < d.na; i += G) W[L.act + i] = ST_LD(a.s.act, (size_t)e * d.na + i);
-  real time = a.s.time[e];
-  E.status = a.s.status ? a.s.status[e] : 0;
-  const __attribute__((address_space(4))) mm_task& t = KA().t;
-  // ---- action -> ctrl (BaseV0.step: base_v0.py:82-108)
-  const bool has_ro = a.mode == 2 && a.has_ro && !obs_only;
-  int badc = 0;
-  // reafferentation overwrites ctrl[reaf_dst] below (base_v0.py:104-108): what the policy sent to THAT actuator never reaches
-  // mj_fwdActuation, so it is not part of the bad-control test (the source's value is: it is what the destination receives)
-  const int reaf_skip = (a.mode == 2 && !obs_only && t.reaf_src >= 0 && t.reaf_dst >= 0) ? t.reaf_dst : -1;
-  for (int u = g; u < d.nu; u += G) {
-    real c = a.ctrl ? a.ctrl[(size_t)e * d.nu + u] : 0.f;
-    if (has_ro && !a.ctrl) {
-      // action ~ U[0,1) drawn here (benchmarks/mjx_benchmark.py:29), element-for-element what mm_uniform writes for the flat
-      // index of (global env, actuator)
-      const uint64_t i = (uint64_t)(a.s.env_index_base + e) * (uint64_t)d.nu + (uint64_t)u, i4 = i >> 2;
-      const uint64_t sd = KA().ro.action_seed, sm = KA().ro.action_stream;
-      uint32_t cc[4] = {(uint32_t)i4, (uint32_t)(i4 >> 32), (uint32_t)sm, (uint32_t)(sm >> 32)};
-      philox4x32_10(cc, (uint32_t)sd, (uint32_t)(sd >> 32));
-      const int w = (int)(i & 3);
-      c = u01(w == 0 ? cc[0] : (w == 1 ? cc[1] : (w == 2 ? cc[2] : cc[3])));
-      if (KA().ro.action_out && !dup) KA().ro.action_out[(size_t)e * d.nu + u] = c;
-    }
-    const bool mus = MI_(ACT_DYNTYPE)[u] == MM_DYN_MUSCLE;
-    if (obs_only) c = 0.f;
-    if (a.mode == 2 && !obs_only && t.normalize_act && mus) c = 1.f / (1.f + m_exp(-5.f * (c - 0.5f)));
-    // no activation states at all (motorFinger): BaseV0.step hands the normalisation to the robot, which maps [-1, 1] onto
-    // the ctrl range (base_v0.py:94-96, robot.py:786-796)
-    if (a.mode == 2 && !obs_only && t.normalize_act && d.na == 0)
-      c = 0.5f * (MF_(ACT_CTRLRANGE)[2 * u] + MF_(ACT_CTRLRANGE)[2 * u + 1]) +
-          c * 0.5f * (MF_(ACT_CTRLRANGE)[2 * u + 1] - MF_(ACT_CTRLRANGE)[2 * u]);
-    if (a.mode == 2 && !obs_only && t.fatigue && mus) {
-      // 3CC-r muscle fatigue (fatigue.py:38-76), dt = timestep * frame_skip
-      int aa = MI_(ACT_ACTADR)[u];
-      size_t k = (size_t)e * d.na + aa;
-      real MA = t.fat_MA[k], MR = t.fat_MR[k], MF = t.fat_MF[k], TL = c;
-      real dt = d.timestep * (real)t.nsubsteps;
-      real tauact = MF_(ACT_DYNPRM)[3 * u], taudeact = MF_(ACT_DYNPRM)[3 * u + 1];
-      real LD = 1.f / tauact * (0.5f + 1.5f * MA), LR = (0.5f + 1.5f * MA) / taudeact;
-      real C, rR;
-      if (MA < TL) { C = MR > (TL - MA) ? LD * (TL - MA) : LD * MR; rR = t.fat_R; }
-      else { C = LR * (TL - MA); rR = t.fat_r * t.fat_R; }
-      real lo = m_max(-MA / dt + t.fat_F * MA, (MR - 1.f) / dt + rR * MF);
-      real hi = m_min((1.f - MA) / dt + t.fat_F * MA, MR / dt + rR * MF);
-      C = m_min(m_max(C, lo), hi);
-      real dMA = (C - t.fat_F * MA) * dt, dMR = (-C + rR * MF) * dt, dMF = (t.fat_F * MA - rR * MF) * dt;
-      MA += dMA; MR += dMR; MF += dMF;
-      if (!dup) { t.fat_MA[k] = MA; t.fat_MR[k] = MR; t.fat_MF[k] = MF; }
-      c = MA;
-    }
-    if (MM_BADCTRL_CHECK == 1) badc |= (u != reaf_skip) & !(m_abs(c) < 1e10f);
-    W[L.ctrl + u] = c;
-  }
-  GSYNC();
-  if (a.mode == 2 && !obs_only && t.reaf_src >= 0 && t.reaf_dst >= 0 && g == 0) {  // base_v0.py:104-108
-    W[L.ctrl + t.reaf_dst] = W[L.ctrl + t.reaf_src];
-    W[L.ctrl + t.reaf_src] = 0.f;
-  }
-  GSYNC();
-  if (MM_BADCTRL_CHECK) {  // mj_fwdActuation's control check (mjWARN_BADCTRL): a NaN / Inf / huge entry zeroes ALL controls of the env, the state is kept
-    if (MM_BADCTRL_CHECK == 2) for (int u = g; u < d.nu; u += G) badc |= !(m_abs(W[L.ctrl + u]) < 1e10f);
-    if (gor<G>(badc)) {
-      for (int u = g; u < d.nu; u += G) W[L.ctrl + u] = 0.f;
-      E.status |= 32;
-      GSYNC();
-    }
-  }
-  if (a.mode == 2 && t.ctrl_out && !dup)
-    for (int u = g; u < d.nu; u += G) t.ctrl_out[(size_t)e * d.nu + u] = W[L.ctrl + u];
-
-  int nsub = (OBS || a.mode == 1 || obs_only) ? 0 : t.nsubsteps;
-  bool fwd = OBS || a.mode == 1 || obs_only || (a.mode == 2 && t.do_forward);
-  // hash of the state rows (and per-env model deltas) of this env as they sit in HBM: the key of its forward-carry row
-  auto carry_hash = [&]() -> unsigned {
-    unsigned h = 0u;
-    for (int i = g; i < d.nq; i += G) h ^= carry_mix((float)W[L.qpos + i], (unsigned)i);
-    if (g < d.nv) h ^= carry_mix((float)E.d_qvel, 1024u + g) ^ carry_mix((float)E.d_warm, 2048u + g);
-    for (int i = g; i < d.na; i += G) h ^= carry_mix((float)W[L.act + i], 3072u + i);
-    if (g == 0) {
-      if constexpr (GEN) {      // per-env collision geometry (reorient): part of what the forward pass saw
-        if (E.env_has_gs) h ^= carry_mix((float)E.env_gsv[0], 4100u) ^ carry_mix((float)E.env_gsv[1], 4101u) ^ carry_mix((float)E.env_gsv[2], 4102u);
-        h ^= carry_mix(__int_as_float(E.env_gtype), 4103u);
-      }
-      if (a.s.body_mass_env) h ^= carry_mix(a.s.body_mass_env[e], 4096u);
-      if (a.s.body_pos_env) h ^= carry_mix(a.s.body_pos_env[(size_t)e * 3], 4097u) ^ carry_mix(a.s.body_pos_env[(size_t)e * 3 + 1], 4098u) ^ carry_mix(a.s.body_pos_env[(size_t)e * 3 + 2], 4099u);
-    }
-    return gxor<G>(h) | 1u;       // never 0: a zeroed row matches nothing
-  };
-  bool carry_row = false;      // this env has a carry row (its address: E.carry_row(), re-derived at every use)
-  if constexpr (Engine<G, NVP, GEN, INTEG>::CARRY) {
-    if (a.mode == 2 && !obs_only && t.fwd_carry) {
-      carry_row = true;
-      const unsigned h = carry_hash();
-      // The decision is made for the WAVE: a group that skipped its first pass while its neighbour ran it would fall one pass behind
-      // -- the helper wave of a two-wave launch serves the passes of all its groups in lockstep (a deadlock until the bounded
-      // waits give up) -- and a wave that runs the pipeline for one of its groups saves nothing by skipping it for the other
-      const bool match = nsub > 0 && (unsigned)__float_as_int(E.carry_row()[0]) == h;
-      if (__ballot(!match) == 0ull) E.carry_in = true;
-      if (fwd && !dup) E.carry_out = true;
-    }
-  }
-  // FOLD: the masked auto-reset of the WALK / REORIENT tasks inside this launch (mm_rollout.autoreset).  Their first observation
-  // needs a forward pass on the reset state: an env that ends its episode is re-armed in registers / LDS after the task stage and
-  // the same wave runs the reset-observation pass (forward + observation, no stepping, no bookkeeping) before the state is stored.
-  // One env per wavefront (G = 64), so the second pass is a wave-uniform branch.  It is a SECOND inlined copy of the forward
-  // pipeline and of the task stage (forward only, obs_only constant), not a loop around one copy: the loop kept everything the
-  // pipeline reads live across the task stage and the reset block (100+ VGPR spills in the 32- / 36-wide kernels, kernel time
-  // +1..3 %); the straight-line form has the spill count and the kernel time of the unfolded kernel (0 / 0 / 5 spills), and the
-  // cold copy is only fetched by a wave whose env resets.  Compiled into the kernels that also exist as reset-observation kernels
-  // (MM_KERNELS_OBS: the 32- and 36-wide ones of the reorient and leg models) -- the only models the two tasks run on.
-  constexpr bool FOLD = MM_FOLD_RESET && GEN && G == 64 && !OBS && (NVP == 32 || NVP == 36);
-  bool refold = false;
-  // results of the task stage the rollout bookkeeping needs: dense reward / solved / done (valid in lane 0 of the group),
-  // and whether this env is re-armed inside this launch (group-uniform; POSE task with mm_rollout.autoreset)
-  real rw_dense = 0.f, rw_solved = 0.f;
-  bool rw_done = false, will_reset = false;
-  E.run(nsub, fwd, time);
-
-  // everything between the pipeline and the state store: derived outputs, task stage, bookkeeping.  `pass` 1 = the reset-observation
-  // pass of a folded reset (observation only: obs_only is true there)
-  auto stage = [&](const bool obs_only, const int pass) __attribute__((always_inline)) {
-  // ---- derived outputs of the final forward
-  if (fwd && a.has_derived) {
-    const mm_derived& o = a.o;
-    const bool isb = g < d.nbody;
-    const V3 org = E.origin();   // outputs are world coordinates
-    if (o.xpos && isb) st3(o.xpos + ((size_t)e * d.nbody + g) * 3, E.b_xpos + org);
-    if (o.xquat && isb) { float* q = o.xquat + ((size_t)e * d.nbody + g) * 4; q[0] = E.b_xquat.w; q[1] = E.b_xquat.x; q[2] = E.b_xquat.y; q[3] = E.b_xquat.z; }
-    if (o.xipos && isb) st3(o.xipos + ((size_t)e * d.nbody + g) * 3, E.b_xipos + org);
-    if (o.cvel && isb) for (int k = 0; k < 6; k++) o.cvel[((size_t)e * d.nbody + g) * 6 + k] = E.b_cvel[k];
-    if (o.subtree_com && isb) st3(o.subtree_com + ((size_t)e * d.nbody + g) * 3, ld3(W + L.com + 3 * AUXI(body_rootslot)[g]) + org);
-    if (o.site_xpos)
-      for (int s = g; s < d.nsite; s += G) st3(o.site_xpos + ((size_t)e * d.nsite + s) * 3, E.site_pos(s) + org);
-    if (o.geom_xpos)
-      for (int s = g; s < d.ngeom; s += G) st3(o.geom_xpos + ((size_t)e * d.ngeom + s) * 3, E.geom_pos(s) + org);
-    if (o.actuator_length) for (int i = g; i < d.nu; i += G) o.actuator_length[(size_t)e * d.nu + i] = W[L.actlen + i];
-    if (o.actuator_velocity) for (int i = g; i < d.nu; i += G) o.actuator_velocity[(size_t)e * d.nu + i] = W[L.actvel + i];
-    if (o.actuator_force) for (int i = g; i < d.nu; i += G) o.actuator_force[(size_t)e * d.nu + i] = W[L.actfrc + i];
-    if (o.qacc && g < d.nv) o.qacc[(size_t)e * d.nv + g] = E.d_qacc;
-    if (o.ten_length) for (int i = g; i < d.ntendon; i += G) o.ten_length[(size_t)e * d.ntendon + i] = W[L.tenlen + i];
-    if (g == 0 && o.nefc) o.nefc[e] = E.nefc;
-    if (g == 0 && o.solver_niter) o.solver_niter[e] = E.niter;
-  }
-  if (a.dbg) {  // tests only: owner registers and tables in a flat record
-    float* D = a.dbg + (size_t)e * a.D.total;
-    if constexpr (Engine<G, NVP, GEN, INTEG>::SP) {
-      E.sp_dense_tile();
-      if (g < d.nv) for (int k = 0; k < d.nv; k++) D[a.D.M + g * d.nv + k] = W[L.u1 + g * Engine<G, NVP, GEN, INTEG>::TD + k];
-    }
-    if (g < d.nbody) {
-      st3(D + a.D.xpos + 3 * g, E.b_xpos + E.origin()); st3(D + a.D.xipos + 3 * g, E.b_xipos + E.origin());
-      D[a.D.xquat + 4 * g] = E.b_xquat.w; D[a.D.xquat + 4 * g + 1] = E.b_xquat.x;
-      D[a.D.xquat + 4 * g + 2] = E.b_xquat.y; D[a.D.xquat + 4 * g + 3] = E.b_xquat.z;
-      for (int k = 0; k < 6; k++) D[a.D.cvel + 6 * g + k] = E.b_cvel[k];
-    }
-    if (g < d.nv) {
-      for (int k = 0; k < 6; k++) D[a.D.cdof + 6 * g + k] = E.d_cdof[k];
-      if constexpr (!Engine<G, NVP, GEN, INTEG>::SP) {
-#pragma unroll
-        for (int k = 0; k < NVP; k++) if (k < d.nv) D[a.D.M + g * d.nv + k] = E.Mrow[k];
-      }
-      D[a.D.bias + g] = E.d_bias; D[a.D.smooth + g] = E.d_smooth; D[a.D.qaccsm + g] = E.d_qaccsm;
-      D[a.D.qacc + g] = E.d_qacc; D[a.D.qfrccon + g] = E.d_qfrccon;
-    }
-    for (int i = g; i < d.ntendon; i += G) { D[a.D.tenlen + i] = W[L.tenlen + i]; D[a.D.tenvel + i] = W[L.tenvel + i]; }
-    for (int i = g; i < d.ntenJ; i += G) D[a.D.tenj + i] = W[L.tenj + i];
-    for (int i = g; i < d.nu; i += G) D[a.D.actfrc + i] = W[L.actfrc + i];
-    for (int i = g; i < d.na; i += G) D[a.D.actdot + i] = W[L.actdot + i];
-#if MM_NEWTON_TRACE
-    if constexpr (GEN) {   // the last eight rows of efc_J over the M slot of the record
-      const int r0 = E.nefc > 8 ? E.nefc - 8 : 0;
-      if (g < d.nv) for (int r = 0; r < 8; r++) D[a.D.M + r * d.nv + g] = (float)E.Jrow(r0 + r)[g];
-    }
-#endif
-#if MM_NEWTON_TRACE
-    if constexpr (GEN) { const real j2_ = E.jac_mul(E.d_qacc) - E.r_aref; D[a.D.scal + 32 + 48 + (g & 15)] = 0.f; if (g >= 16 && g < 32) D[a.D.scal + 32 + 48 + g - 16] = (float)j2_; }   // rows 16..31: J qacc - aref recomputed
-#endif
-    D[a.D.efc_active + g] = MM_NEWTON_TRACE ? (float)E.r_jar : (E.r_active ? 1.f : 0.f); D[a.D.efc_D + g] = E.r_D; D[a.D.efc_aref + g] = E.r_aref;   // (trace build: the solver's running J a - aref of row g)
-    if (g == 0) D[a.D.scal] = (real)E.niter;
-    if (g < 15) { D[a.D.scal + 1 + g] = E.r_jar; D[a.D.scal + 16 + g] = E.r_floss; }   // rows of small test models
-  }
-  if (MM_STAGE_PROF && a.prof && blockIdx.x == 0 && threadIdx.x == 0) {
-    E.pf[MM_STAGE_PROF ? PF_TOTAL : 0] = clock64() - t_start;
-#pragma unroll
-    for (int i = 0; i < (MM_STAGE_PROF ? NPROF : 1); i++) a.prof[i] = E.pf[i];
-  }
-
-  // ---- task stage: obs_dict / reward_dict (pose_v0.py:100-140), TimeLimit counter
-  if (a.mode == 2) {
-    int sc = 0, sc0 = 0;
-    if (t.step_count) { sc0 = (FOLD && pass == 1) ? 0 : t.step_count[e]; sc = obs_only ? sc0 : sc0 + 1; }
-    if (t.task == MM_TASK_POSE) {
-      const real dt = t.obs_dt;
-      const int o_err = t.obs_layout == 1 ? d.nq + d.nv + d.na : d.nq + d.nv;
-      const int o_act = t.obs_layout == 1 ? d.nq + d.nv : 2 * d.nq + d.nv;
-      real err2 = 0.f, act2 = 0.f;
-      float* ob = t.obs ? t.obs + (size_t)e * t.obs_dim : nullptr;
-      for (int i = g; i < d.nq; i += G) {
-        const real pe = t.target_jnt_value[(size_t)e * d.nq + i] - W[L.qpos + i];
-        err2 += pe * pe;
-      }
-      for (int i = g; i < d.na; i += G) { const real x = W[L.act + i]; act2 += x * x; }
-      err2 = gsum<G>(err2); act2 = gsum<G>(act2);
-      // group-uniform (gsum is bitwise uniform): every lane knows whether the episode ends here
-      const real pose_dist = m_sqrt(err2);
-      const bool done = pose_dist > t.far_th;
-      rw_done = done;
-      will_reset = has_ro && KA().ro.autoreset && (done || (t.max_episode_steps > 0 && sc >= t.max_episode_steps));
-      if (ob && !will_reset) {      // an env that resets in this launch gets the first observation of its new episode instead
-        for (int i = g; i < d.nq; i += G) {
-          const real q = W[L.qpos + i];
-          ob[i] = q; ob[o_err + i] = t.target_jnt_value[(size_t)e * d.nq + i] - q;
-        }
-        if (g < d.nv) ob[d.nq + g] = E.d_qvel * dt;
-        for (int i = g; i < d.na; i += G) ob[o_act + i] = W[L.act + i];
-      }
-      if (g == 0) {
-        real act_mag = m_sqrt(act2);
-        if (d.na != 0 && t.act_reg_mean) act_mag = act_mag / (real)d.na;
-        real r_pose = -pose_dist;
-        real r_bonus = (pose_dist < t.pose_thd ? 1.f : 0.f) + (pose_dist < 1.5f * t.pose_thd ? 1.f : 0.f);
-        real r_pen = pose_dist > t.far_th ? -1.f : 0.f;
-        real r_act = -act_mag;
-        rw_dense = t.w_pose * r_pose + t.w_bonus * r_bonus + t.w_act_reg * r_act + t.w_penalty * r_pen;
-        rw_solved = pose_dist < t.pose_thd ? 1.f : 0.f;
-        if (t.rwd && !obs_only) {   // the reset observation leaves the terminal step's reward terms in place
-          float* r = t.rwd + (size_t)e * MM_RWD_COUNT;
-          r[MM_RWD_POSE] = r_pose; r[MM_RWD_BONUS] = r_bonus; r[MM_RWD_PENALTY] = r_pen; r[MM_RWD_ACT_REG] = r_act;
-          r[MM_RWD_SPARSE] = -pose_dist; r[MM_RWD_SOLVED] = rw_solved;
-          r[MM_RWD_DONE] = done ? 1.f : 0.f;
-          r[MM_RWD_DENSE] = rw_dense;
-        }
-        if (t.done && !obs_only) t.done[e] = done ? 1 : 0;
-      }
-    }
-    if (t.task == MM_TASK_REACH) {
-      // obs [qpos, qvel*dt, tip_pos, reach_err, act]; reward dict of reach_v0.py:123-151
-      const int n3 = 3 * t.ntip;
-      // obs_layout 1 = MJX order [qpos, qvel, act, tip_pos, reach_err] (playground_reach_v0.py:150-165)
-      const int o_tip = t.obs_layout == 1 ? d.nq + d.nv + d.na : d.nq + d.nv;
-      const int o_ract = t.obs_layout == 1 ? d.nq + d.nv : d.nq + d.nv + 2 * n3;
-      real err2 = 0.f, act2 = 0.f;
-      float* ob = t.obs ? t.obs + (size_t)e * t.obs_dim : nullptr;
-      for (int i = g; i < d.nq; i += G) if (ob) ob[i] = W[L.qpos + i];
-      if (ob && g < d.nv) ob[d.nq + g] = E.d_qvel * t.obs_dt;
-      const real vs = g < d.nv ? E.d_qvel * t.obs_dt : 0.f;
-      const real vel2 = t.reach_stand ? gsum<G>(vs * vs) : 0.f;
-      for (int i = g; i < t.ntip; i += G) {
-        const V3 tip_i = E.site_pos(t.tip_sites[i]);
-        V3 tip = tip_i + E.origin();
-        V3 tgt = ld3(t.target_pos + (size_t)e * n3 + 3 * i);
-        V3 er = (tgt - E.origin()) - tip_i;
-        err2 += dot(er, er);
-        if (ob) { st3(ob + o_tip + 3 * i, tip); st3(ob + o_tip + n3 + 3 * i, er); }
-      }
-      for (int i = g; i < d.na; i += G) {
-        real x = W[L.act + i];
-        act2 += x * x;
-        if (ob) ob[o_ract + i] = x;
-      }
-      err2 = gsum<G>(err2); act2 = gsum<G>(act2);
-      if (g == 0) {
-        real reach_dist = m_sqrt(err2), act_mag = d.na != 0 ? m_sqrt(act2) / (real)d.na : 0.f;
-        real far_th = time > 2.f * t.obs_dt ? t.reach_far_th * (real)t.ntip : INFINITY;
-        real near_th = (real)t.ntip * (t.reach_stand ? 0.050f : 0.0125f);
-        real r_reach = -reach_dist;
-        if (t.reach_stand) { r_reach = 10.f - reach_dist - 10.f * m_sqrt(vel2); act_mag *= 100.f; }   // walk_v0.py:100-111
-        real r_bonus = (reach_dist < 2.f * near_th ? 1.f : 0.f) + (reach_dist < near_th ? 1.f : 0.f);
-        real r_pen = reach_dist > far_th ? -1.f : 0.f;
-        bool done = reach_dist > far_th;
-        rw_done = done; rw_solved = reach_dist < near_th ? 1.f : 0.f;
-        rw_dense = t.w_pose * r_reach + t.w_bonus * r_bonus + t.w_act_reg * (-act_mag) + t.w_penalty * r_pen;
-        if (t.rwd && !obs_only) {
-          float* r = t.rwd + (size_t)e * MM_RWD_COUNT;
-          r[MM_RWD_POSE] = r_reach; r[MM_RWD_BONUS] = r_bonus; r[MM_RWD_PENALTY] = r_pen; r[MM_RWD_ACT_REG] = -act_mag;
-          r[MM_RWD_SPARSE] = -reach_dist; r[MM_RWD_SOLVED] = reach_dist < near_th ? 1.f : 0.f;
-          r[MM_RWD_DONE] = done ? 1.f : 0.f;
-          r[MM_RWD_DENSE] = t.w_pose * r_reach + t.w_bonus * r_bonus + t.w_act_reg * (-act_mag) + t.w_penalty * r_pen;
-        }
-        if (t.done && !obs_only) t.done[e] = done ? 1 : 0;
-      }
-    }
-    if (t.task == MM_TASK_WALK) {
-      // obs / reward of WalkEnvV0 (walk_v0.py:283-325, 367-540); self.steps == step_count BEFORE this step's increment
-      float* ob = t.obs ? t.obs + (size_t)e * t.obs_dim : nullptr;
-      const int nq2 = d.nq - 2;
-      const int o_qv = nq2, o_cv = o_qv + d.nv, o_tq = o_cv + 2, o_fh = o_tq + 4, o_h = o_fh + 2, o_fr = o_h + 1,
-                o_ph = o_fr + 6, o_ml = o_ph + 1, o_mv = o_ml + d.nu, o_mf = o_mv + d.nu, o_act = o_mf + d.nu;
-      const bool isb = g > 0 && g < d.nbody;
-      real ms = isb ? MF_(BODY_MASS)[g] : 0.f;
-      if (a.s.body_mass_env && g == a.s.body_mass_env_id) ms = a.s.body_mass_env[e];
-      const real mtot = gsum<G>(ms);
-      // com velocity with the reference's sign convention: mean of -cvel[:, 3:5]
-      const real cvx = gsum<G>(ms * -E.b_cvel[3]) / mtot, cvy = gsum<G>(ms * -E.b_cvel[4]) / mtot;
-      const real height = gsum<G>(ms * E.b_xipos.z) / mtot + d.oz;
-      const int bp = t.walk_body[0], bt = t.walk_body[1], bl = t.walk_body[2], br = t.walk_body[3];
-      const V3 xp = v3(bc<G>(E.b_xpos.x, bp), bc<G>(E.b_xpos.y, bp), bc<G>(E.b_xpos.z, bp));
-      const V3 xl = v3(bc<G>(E.b_xpos.x, bl), bc<G>(E.b_xpos.y, bl), bc<G>(E.b_xpos.z, bl));
-      const V3 xr = v3(bc<G>(E.b_xpos.x, br), bc<G>(E.b_xpos.y, br), bc<G>(E.b_xpos.z, br));
-      const real tq0 = bc<G>(E.b_xquat.w, bt), tq1 = bc<G>(E.b_xquat.x, bt), tq2 = bc<G>(E.b_xquat.y, bt), tq3 = bc<G>(E.b_xquat.z, bt);
-      const real phase = m_fmod((real)sc0 / (real)t.walk_hip_period, 1.f);
-      real act2 = 0.f;
-      if (ob) {
-        for (int i = g; i < nq2; i += G) ob[i] = W[L.qpos + 2 + i];
-        if (g < d.nv) ob[o_qv + g] = E.d_qvel * t.obs_dt;
-      }
-      for (int i = g; i < d.nu; i += G) {
-        if (ob) {
-          ob[o_ml + i] = W[L.actlen + i];
-          ob[o_mv + i] = clampf(W[L.actvel + i], -100.f, 100.f);
-          ob[o_mf + i] = clampf(W[L.actfrc + i] / 1000.f, -100.f, 100.f);
-        }
-      }
-      for (int i = g; i < d.na; i += G) {
-        real x = W[L.act + i];
-        act2 += x * x;
-        if (ob) ob[o_act + i] = x;
-      }
-      act2 = gsum<G>(act2);
-      if (g == 0) {
-        if (ob) {
-          ob[o_cv] = cvx; ob[o_cv + 1] = cvy;
-          ob[o_tq] = tq0; ob[o_tq + 1] = tq1; ob[o_tq + 2] = tq2; ob[o_tq + 3] = tq3;
-          ob[o_fh] = xl.z + d.oz; ob[o_fh + 1] = xr.z + d.oz;
-          ob[o_h] = height;
-          st3(ob + o_fr, xl - xp); st3(ob + o_fr + 3, xr - xp);
-          ob[o_ph] = phase;
-        }
-        const real* q = W + L.qpos;
-        const real dvy = t.walk_target_y_vel - cvy, dvx = t.walk_target_x_vel - cvx;
-        const real vel_reward = m_exp(-dvy * dvy) + m_exp(-dvx * dvx);
-        const real two_pi = 6.283185307179586f;
-        const real des_l = 0.8f * m_cos(phase * two_pi + 3.141592653589793f), des_r = 0.8f * m_cos(phase * two_pi);
-        const real el = des_l - q[t.walk_qadr[0]], er = des_r - q[t.walk_qadr[1]];
-        const real cyclic_hip = m_sqrt(el * el + er * er);
-        real rr = 0.f;
-        for (int k = 0; k < 4; k++) { real dq = 5.f * (q[3 + k] - t.walk_target_rot[k]); rr += dq * dq; }
-        const real ref_rot = m_exp(-m_sqrt(rr));
-        const real mag = 0.25f * (m_abs(q[t.walk_qadr[2]]) + m_abs(q[t.walk_qadr[3]]) + m_abs(q[t.walk_qadr[4]]) + m_abs(q[t.walk_qadr[5]]));
-        const real joint_angle_rew = m_exp(-5.f * mag);
-        const real act_mag = d.na != 0 ? m_sqrt(act2) / (real)d.na : 0.f;
-        // |(quat2mat(qpos[3:7]) @ [1,0,0])[0]| > max_rot   (walk_v0.py:514-526)
-        const real nq_ = q[3] * q[3] + q[4] * q[4] + q[5] * q[5] + q[6] * q[6];   // quat_math.py:151-174
-        const real r00 = nq_ > 1.1920929e-07f * 4.f ? 1.f - (2.f / nq_) * (q[5] * q[5] + q[6] * q[6]) : 1.f;
-        const bool done = height < t.walk_min_height || m_abs(r00) > t.walk_max_rot;
-        rw_done = done; rw_solved = vel_reward >= 1.f ? 1.f : 0.f;
-        rw_dense = t.walk_w[0] * vel_reward + t.walk_w[1] * (done ? 1.f : 0.f) + t.walk_w[2] * cyclic_hip +
-                   t.walk_w[3] * ref_rot + t.walk_w[4] * joint_angle_rew;
-        if (t.rwd && !obs_only) {   // the reset observation leaves the terminal step's reward terms in place
-          float* r = t.rwd + (size_t)e * MM_RWDW_COUNT;
-          r[MM_RWDW_VEL] = vel_reward; r[MM_RWDW_CYCLIC_HIP] = cyclic_hip; r[MM_RWDW_REF_ROT] = ref_rot;
-          r[MM_RWDW_JOINT_ANGLE] = joint_angle_rew; r[MM_RWDW_ACT_MAG] = act_mag; r[MM_RWDW_SPARSE] = vel_reward;
-          r[MM_RWDW_SOLVED] = vel_reward >= 1.f ? 1.f : 0.f; r[MM_RWDW_DONE] = done ? 1.f : 0.f;
-          r[MM_RWDW_DENSE] = t.walk_w[0] * vel_reward + t.walk_w[1] * (done ? 1.f : 0.f) + t.walk_w[2] * cyclic_hip +
-                             t.walk_w[3] * ref_rot + t.walk_w[4] * joint_angle_rew;
-        }
-        if (t.done && !obs_only) t.done[e] = done ? 1 : 0;
-      }
-    }
-    if (t.task == MM_TASK_OBJHOLD) {
-      // obs / reward of ObjHoldFixedEnvV0 (obj_hold_v0.py:82-131)
-      float* ob = t.obs ? t.obs + (size_t)e * t.obs_dim : nullptr;
-      const int nh = d.nq - 7, nhv = d.nv - 6;
-      real act2 = 0.f;
-      if (ob) {
-        for (int i = g; i < nh; i += G) ob[i] = W[L.qpos + i];
-        if (g < nhv) ob[nh + g] = E.d_qvel * t.obs_dt;
-      }
-      for (int i = g; i < d.na; i += G) {
-        real x = W[L.act + i];
-        act2 += x * x;
-        if (ob) ob[nh + nhv + 6 + i] = x;
-      }
-      act2 = gsum<G>(act2);
-      if (g == 0) {
-        const V3 op_i = E.site_pos(t.tip_sites[0]);
-        const V3 op = op_i + E.origin();
-        const V3 er = (ld3(t.target_pos + (size_t)e * 3) - E.origin()) - op_i;
-        if (ob) { st3(ob + nh + nhv, op); st3(ob + nh + nhv + 3, er); }
-        const real goal_dist = m_sqrt(dot(er, er)), act_mag = d.na != 0 ? m_sqrt(act2) / (real)d.na : 0.f;
-        const real goal_th = 0.010f;
-        const bool drop = goal_dist > 0.300f;
-        const real bonus = (goal_dist < 2.f * goal_th ? 1.f : 0.f) + (goal_dist < goal_th ? 1.f : 0.f);
-        rw_done = drop; rw_solved = goal_dist < goal_th ? 1.f : 0.f;
-        rw_dense = t.w_pose * -goal_dist + t.w_bonus * bonus + t.w_act_reg * -act_mag + t.w_penalty * (drop ? -1.f : 0.f);
-        if (t.rwd && !obs_only) {
-          float* r = t.rwd + (size_t)e * MM_RWD_COUNT;
-          r[MM_RWD_POSE] = -goal_dist; r[MM_RWD_BONUS] = bonus; r[MM_RWD_PENALTY] = drop ? -1.f : 0.f; r[MM_RWD_ACT_REG] = -act_mag;
-          r[MM_RWD_SPARSE] = -goal_dist; r[MM_RWD_SOLVED] = goal_dist < goal_th ? 1.f : 0.f; r[MM_RWD_DONE] = drop ? 1.f : 0.f;
-          r[MM_RWD_DENSE] = t.w_pose * -goal_dist + t.w_bonus * bonus + t.w_act_reg * -act_mag + t.w_penalty * (drop ? -1.f : 0.f);
-        }
-        if (t.done && !obs_only) t.done[e] = drop ? 1 : 0;
-      }
-    }
-    if (t.task == MM_TASK_KEYTURN) {
-      // obs / reward of KeyTurnEnvV0 (key_turn_v0.py:101-150)
-      float* ob = t.obs ? t.obs + (size_t)e * t.obs_dim : nullptr;
-      const int nh = d.nq - 1, nhv = d.nv - 1;
-      const int o_kq = nh + nhv, o_if = o_kq + 2, o_th = o_if + 3, o_act = o_th + 3;
-      real act2 = 0.f;
-      if (ob) {
-        for (int i = g; i < nh; i += G) ob[i] = W[L.qpos + i];
-        if (g < nhv) ob[nh + g] = E.d_qvel * t.obs_dt;
-        if (g == nhv) ob[o_kq + 1] = E.d_qvel * t.obs_dt;
-      }
-      for (int i = g; i < d.na; i += G) {
-        real x = W[L.act + i];
-        act2 += x * x;
-        if (ob) ob[o_act + i] = x;
-      }
-      act2 = gsum<G>(act2);
-      if (g == 0) {
-        const V3 kh = E.site_pos(t.tip_sites[0]);
-        const V3 ifa = kh - E.site_pos(t.tip_sites[1]), tha = kh - E.site_pos(t.tip_sites[2]);
-        const real key_pos = W[L.qpos + nh];
-        if (ob) { ob[o_kq] = key_pos; st3(ob + o_if, ifa); st3(ob + o_th, tha); }
-        const real ifd = m_abs(m_sqrt(dot(ifa, ifa)) - 0.030f), thd = m_abs(m_sqrt(dot(tha, tha)) - 0.030f);
-        const real act_mag = d.na != 0 ? m_sqrt(act2) / (real)d.na : 0.f;
-        const real far_th = 0.1f, pi_ = 3.14159265358979f;
-        const real bonus = (key_pos > 0.5f * pi_ ? 1.f : 0.f) + (key_pos > pi_ ? 1.f : 0.f);
-        const real penalty = -(ifd > 0.5f * far_th ? 1.f : 0.f) - (thd > 0.5f * far_th ? 1.f : 0.f);
-        const bool done = ifd > far_th || thd > far_th;
-        rw_done = done; rw_solved = key_pos > t.key_goal_th ? 1.f : 0.f;
-        rw_dense = t.key_w[0] * key_pos + t.key_w[1] * -ifd + t.key_w[2] * -thd + t.key_w[3] * -act_mag +
-                   t.key_w[4] * bonus + t.key_w[5] * penalty;
-        if (t.rwd && !obs_only) {
-          float* r = t.rwd + (size_t)e * MM_RWDK_COUNT;
-          r[MM_RWDK_KEY_TURN] = key_pos; r[MM_RWDK_IF_APPROACH] = -ifd; r[MM_RWDK_TH_APPROACH] = -thd; r[MM_RWDK_ACT_REG] = -act_mag;
-          r[MM_RWDK_BONUS] = bonus; r[MM_RWDK_PENALTY] = penalty; r[MM_RWDK_SPARSE] = key_pos;
-          r[MM_RWDK_SOLVED] = key_pos > t.key_goal_th ? 1.f : 0.f; r[MM_RWDK_DONE] = done ? 1.f : 0.f;
-          r[MM_RWDK_DENSE] = t.key_w[0] * key_pos + t.key_w[1] * -ifd + t.key_w[2] * -thd + t.key_w[3] * -act_mag +
-                             t.key_w[4] * bonus + t.key_w[5] * penalty;
-        }
-        if (t.done && !obs_only) t.done[e] = done ? 1 : 0;
-      }
-    }
-    if (t.task == MM_TASK_REORIENT) {
-      // obs / reward of ProprioceptiveEnvV0 (reorient_sar_v0.py:116-174)
-      float* ob = t.obs ? t.obs + (size_t)e * t.obs_dim : nullptr;
-      const int nh = d.nq - 6;
-      const int o_pos = nh, o_vel = o_pos + 3, o_rot = o_vel + 6, o_des = o_rot + 3, o_ep = o_des + 3, o_er = o_ep + 3,
-                o_ml = o_er + 3, o_mv = o_ml + d.nu, o_mf = o_mv + d.nu, o_act = t.reor_obs_muscle ? o_mf + d.nu : o_ml;
-      real act2 = 0.f;
-      if (ob) {
-        for (int i = g; i < nh; i += G) ob[i] = W[L.qpos + i];
-        if (g < d.nv && g >= d.nv - 6) ob[o_vel + g - (d.nv - 6)] = E.d_qvel * t.obs_dt;
-        if (t.reor_obs_muscle)
-          for (int i = g; i < d.nu; i += G) { ob[o_ml + i] = W[L.actlen + i]; ob[o_mv + i] = W[L.actvel + i]; ob[o_mf + i] = W[L.actfrc + i]; }
-      }
-      for (int i = g; i < d.na; i += G) {
-        real x = W[L.act + i];
-        act2 += x * x;
-        if (ob) ob[o_act + i] = x;
-      }
-      act2 = gsum<G>(act2);
-      if (g == 0) {
-        const int bo = t.reor_obj_body;
-        const V3 opos_i = ld3(W + L.xpos + 3 * bo);
-        const V3 opos = opos_i + E.origin();
-        const real* R = W + L.xmat + 9 * bo;
-        const real sc_ = 2.f * t.reor_axis_half[e] / t.reor_pen_length;   // pen_v0.py: the same vector through the top / bottom sites
-        V3 orot = v3(R[2] * sc_, R[5] * sc_, R[8] * sc_);
-        V3 odes = ld3(t.reor_des_rot + (size_t)e * 3);
-        V3 epos = opos_i - E.site_pos(t.reor_eps_site), erot = orot - odes;
-        if (ob) { st3(ob + o_pos, opos); st3(ob + o_rot, orot); st3(ob + o_des, odes); st3(ob + o_ep, epos); st3(ob + o_er, erot); }
-        const real pos_align = m_sqrt(dot(epos, epos));
-        real nrm = m_sqrt(dot(orot, orot)) * m_sqrt(dot(odes, odes));
-        if (nrm == 0.f) nrm = 1.f;                                   // vector_math.py:26-32
-        const real rot_align = dot(orot, odes) / nrm;
-        const bool dropped = pos_align > 0.075f;
-        const real act_mag = d.na != 0 ? m_sqrt(act2) / (real)d.na : 0.f;
-        const real bonus = ((rot_align > 0.9f && pos_align < 0.075f) ? 1.f : 0.f) + ((rot_align > 0.95f && pos_align < 0.075f) ? 5.f : 0.f);
-        rw_done = dropped; rw_solved = (rot_align > 0.95f && !dropped) ? 1.f : 0.f;
-        rw_dense = t.reor_w[0] * -pos_align + t.reor_w[1] * rot_align + t.reor_w[2] * -act_mag +
-                   t.reor_w[3] * (dropped ? -1.f : 0.f) + t.reor_w[4] * bonus;
-        if (t.rwd && !obs_only) {
-          float* r = t.rwd + (size_t)e * MM_RWDR_COUNT;
-          r[MM_RWDR_POS_ALIGN] = -pos_align; r[MM_RWDR_ROT_ALIGN] = rot_align; r[MM_RWDR_ACT_REG] = -act_mag;
-          r[MM_RWDR_DROP] = dropped ? -1.f : 0.f; r[MM_RWDR_BONUS] = bonus; r[MM_RWDR_SPARSE] = -pos_align + rot_align;
-          r[MM_RWDR_SOLVED] = (rot_align > 0.95f && !dropped) ? 1.f : 0.f; r[MM_RWDR_DONE] = dropped ? 1.f : 0.f;
-          r[MM_RWDR_DENSE] = t.reor_w[0] * -pos_align + t.reor_w[1] * rot_align + t.reor_w[2] * -act_mag +
-                             t.reor_w[3] * (dropped ? -1.f : 0.f) + t.reor_w[4] * bonus;
-        }
-        if (t.done && !obs_only) t.done[e] = dropped ? 1 : 0;
-      }
-    }
-    if constexpr (FOLD) {
-      if (pass == 0 && has_ro && !obs_only && KA().ro.autoreset && (t.task == MM_TASK_WALK || t.task == MM_TASK_REORIENT)) {
-        const bool trunc_ = t.max_episode_steps > 0 && sc >= t.max_episode_steps;
-        refold = __builtin_amdgcn_readfirstlane((int)(rw_done || trunc_)) != 0;     // rw_done is lane 0's
-      }
-    }
-    if (g == 0 && !obs_only) {
-      const bool trunc = t.max_episode_steps > 0 && sc >= t.max_episode_steps;
-      if (t.step_count) t.step_count[e] = (will_reset || refold) ? 0 : sc;
-      if (t.truncated) t.truncated[e] = trunc ? 1 : 0;
-      if (has_ro) {   // rollout bookkeeping (mm_rollout): what mm_episode_stats does in its own launch
-        const __attribute__((address_space(4))) mm_rollout& ro = KA().ro;
-        if (ro.ep_stats) {
-          float* st = ro.ep_stats + (size_t)e * 3;
-          // (fp32 arithmetic on the fp32 reward row's values in every precision mode: what mm_episode_stats adds in its own launch)
-          st[0] += (float)rw_dense; st[1] += 1.f; st[2] = fmaxf(st[2], (float)rw_solved);
-        }
-        if (ro.reset_mask) ro.reset_mask[e] = (rw_done || trunc) ? 1 : 0;
-      }
-    }
-  }
-  };   // stage
-
-  if (!dup) {   // surplus groups never write
-  stage(obs_only, 0);
-  if constexpr (FOLD) {
-    if (refold) {
-      // ---- re-arm this env inside the launch (mm_rollout.autoreset; WALK: mm_walk_reset, REORIENT: mm_reorient_reset_typed --
-      // same Philox counters, keyed by the global env index and the episode counter), then run the reset-observation pass.  The
-      // terminal step's reward / done / statistics are already written; its observation row is replaced by the new episode's.
-      const __attribute__((address_space(4))) mm_rollout& ro = KA().ro;
-      if constexpr (Engine<G, NVP, GEN, INTEG>::TW) {
-        // two-wave launches: nobody waited for the helper's last job of the final forward pass (Euler's factor / the W matrix in
-        // the second tile), which the next forward pass rewrites
-        if (two_wave && (Engine<G, NVP, GEN, INTEG>::IMPL || (!Engine<G, NVP, GEN, INTEG>::SP && d.any_damping && d.eulerdamp))) E.tw_wait(3, E.tw_n);
-      }
-      const int ep = ro.episode[e];
-      const uint32_t ge = (uint32_t)(a.s.env_index_base + e);
-      const uint64_t sd = ro.reset_seed;
-      if (t.task == MM_TASK_WALK) {
-        const float *kq = ro.walk_ka_qpos, *kv = ro.walk_ka_qvel;
-        if (ro.walk_random) {      // walk_v0.py:327-352: coin between the two stride keys, N(0, 0.02) on every coordinate but root height / quaternion
-          uint32_t c[4] = {0xFFFFu, 2u, ge, (uint32_t)ep};
-          philox4x32_10(c, (uint32_t)sd, (uint32_t)(sd >> 32));
-          if (!(u01(c[0]) < 0.5f)) { kq = ro.walk_kb_qpos; kv = ro.walk_kb_qvel; }
-        }
-        for (int i = g; i < d.nq; i += G) {
-          real q = kq[i];
-          if (ro.walk_random && !(i >= 2 && i < 7)) {
-            uint32_t c[4] = {(uint32_t)i, 2u, ge, (uint32_t)ep};
-            philox4x32_10(c, (uint32_t)sd, (uint32_t)(sd >> 32));
-            const real u1 = ((real)(c[0] >> 8) + 0.5f) * (1.0f / 16777216.0f), u2 = u01(c[1]);
-            q += 0.02f * m_sqrt(-2.f * m_log(u1)) * m_cos(6.283185307179586f * u2);
-          }
-          W[L.qpos + i] = q;
-        }
-        if (g < d.nv) { E.d_qvel = kv[g]; W[L.qvel + g] = E.d_qvel; }
-      } else {                     // MM_TASK_REORIENT (reorient_sar_v0.py:386-432)
-        uint32_t c[4] = {0u, 3u, ge, (uint32_t)ep};
-        philox4x32_10(c, (uint32_t)sd, (uint32_t)(sd >> 32));
-        int idx = (int)(u01(c[0]) * (real)ro.reor_ntab);
-        if (idx >= ro.reor_ntab) idx = ro.reor_ntab - 1;
-        int ty = (int)(u01(c[3]) * 4.f);
-        if (ty > 3) ty = 3;
-        const float* sz = ro.reor_size_tables + 3 * (ty * ro.reor_ntab + idx);
-        const real s0 = sz[0], s1 = sz[1], s2 = sz[2];
-        const real ah = ty == 0 ? 1.3f * s1 : (ty == 2 ? s1 : s2);
-        const real e0 = -1.f + 2.f * u01(c[1]), e1 = -0.8f + 2.f * u01(c[2]);
-        const real aj = -0.5f * e1, ak = 0.5f * e0;
-        const real sj = m_sin(aj), cj = m_cos(aj), sk = m_sin(ak), ck = m_cos(ak);
-        const real qw = cj * ck, qx = cj * sk, qy = -(sj * ck), qz = -sj * sk;
-        const real sc_ = 2.f * ah / ro.reor_tar_length;
-        if (g == 0) {             // every lane computed the same draws; lane 0 publishes the per-env model deltas
-          ro.reor_geom_type_env[e] = MM_GEOM_CAPSULE + ty;
-          ro.reor_geom_size_env[(size_t)e * 3] = s0; ro.reor_geom_size_env[(size_t)e * 3 + 1] = s1; ro.reor_geom_size_env[(size_t)e * 3 + 2] = s2;
-          ro.reor_axis_half[e] = ah;
-          ro.reor_des_rot[(size_t)e * 3 + 0] = 2.f * (qx * qz + qw * qy) * sc_;
-          ro.reor_des_rot[(size_t)e * 3 + 1] = 2.f * (qy * qz - qw * qx) * sc_;
-          ro.reor_des_rot[(size_t)e * 3 + 2] = (1.f - 2.f * (qx * qx + qy * qy)) * sc_;
-        }
-        E.env_gtype = MM_GEOM_CAPSULE + ty; E.env_has_gs = true; E.env_gsv[0] = s0; E.env_gsv[1] = s1; E.env_gsv[2] = s2;
-        for (int i = g; i < d.nq; i += G) W[L.qpos + i] = ro.reor_init_qpos[i];
-        if (g < d.nv) { E.d_qvel = 0.f; W[L.qvel + g] = 0.f; }
-      }
-      if (g < d.nv) E.d_warm = 0.f;
-      for (int i = g; i < d.na; i += G) W[L.act + i] = 0.f;
-      for (int u = g; u < d.nu; u += G) W[L.ctrl + u] = 0.f;   // the reset-observation pass runs on ctrl = 0 (mj_resetData; obs_only launches force it too)
-      if (t.fatigue)               // CumulativeFatigue.reset (fatigue.py:82-99): MF = fatigue_reset_vec (or 0), MR = 1 - MF, MA = 0
-        for (int i = g; i < d.na; i += G) {
-          const real mf = ro.fat_reset_vec ? ro.fat_reset_vec[i] : 0.f;
-          const size_t k = (size_t)e * d.na + i;
-          t.fat_MA[k] = 0.f; t.fat_MR[k] = 1.f - mf; t.fat_MF[k] = mf;
-        }
-      time = 0.f; E.status &= 16;      // a reset clears the sticky bits -- except a lost-partner report of this very launch (tw_wait above)
-      if (g == 0) ro.episode[e] = ep + 1;
-      E.reinit_transients();
-      GSYNC();
-#ifndef MM_REFOLD_CARRY
-#define MM_REFOLD_CARRY 0   /* 1: the reset-observation pass of a folded reset also writes a carry row; engine.py's FILE_FLAGS sets it for inst_D */
-#endif
-      if (!MM_REFOLD_CARRY) E.carry_out = false;                 // (the row is voided at the state store)
-      E.template run<MM_REFOLD_CARRY != 0>(0, true, time);
-      stage(true, 1);
-    }
-  }
-  // ---- store state
-  if (!will_reset) {
-    for (int i = g; i < d.nq; i += G) ST_ST(a.s.qpos, (size_t)e * d.nq + i, W[L.qpos + i]);
-    if (g < d.nv) {
-      ST_ST(a.s.qvel, (size_t)e * d.nv + g, E.d_qvel);
-      ST_ST(a.s.qacc_warmstart, (size_t)e * d.nv + g, E.d_warm);
-    }
-    for (int i = g; i < d.na; i += G) ST_ST(a.s.act, (size_t)e * d.na + i, W[L.act + i]);
-    if (g == 0) { a.s.time[e] = time; if (a.s.status) a.s.status[e] = E.status; }
-    if constexpr (Engine<G, NVP, GEN, INTEG>::CARRY) {
-      if (carry_row) {      // stamp the row with the hash of the state just stored (its accelerations were written by the trailing pass), or void it
-        const unsigned h = (E.carry_out && E.status == 0) ? carry_hash() : 0u;
-        if (g == 0) E.carry_row()[0] = __int_as_float((int)h);
-      }
-    }
-  } else {
-    // masked auto-reset of a POSE env folded into this launch: the draws, state and first observation k_reset produces for
-    // mm_pose_reset (pose_v0.py:174-257; Philox counter (i/2, 0, global env, episode): words 0/1 -> qpos, 2/3 -> target)
-    const __attribute__((address_space(4))) mm_rollout& ro = KA().ro;
-    const int ep = ro.episode[e];
-    const uint64_t sd = ro.reset_seed;
-    const int o_err = t.obs_layout == 1 ? d.nq + d.nv + d.na : d.nq + d.nv;
-    const int o_act = t.obs_layout == 1 ? d.nq + d.nv : 2 * d.nq + d.nv;
-    float* ob = t.obs ? t.obs + (size_t)e * t.obs_dim : nullptr;
-    for (int i = g; i < d.nq; i += G) {
-      uint32_t c[4] = {(uint32_t)(i >> 1), 0u, (uint32_t)(a.s.env_index_base + e), (uint32_t)ep};
-      philox4x32_10(c, (uint32_t)sd, (uint32_t)(sd >> 32));
-      // (fp32 arithmetic in every precision mode: the draws are the reset kernel's, bit for bit)
-      const float uq = u01((i & 1) ? c[1] : c[0]), ut = u01((i & 1) ? c[3] : c[2]);
-      const float q = ro.random_qpos ? ro.qlo[i] + (ro.qhi[i] - ro.qlo[i]) * uq : MF_(QPOS0)[i];
-      const float tg = ro.tlo[i] + (ro.thi[i] - ro.tlo[i]) * ut;
-      ST_ST(a.s.qpos, (size_t)e * d.nq + i, q);
-      ro.target[(size_t)e * d.nq + i] = tg;
-      if (ob) { ob[i] = q; ob[o_err + i] = tg - q; }
-    }
-    if (g < d.nv) {
-      ST_ST(a.s.qvel, (size_t)e * d.nv + g, 0.f);
-      ST_ST(a.s.qacc_warmstart, (size_t)e * d.nv + g, 0.f);
-      if (ob) ob[d.nq + g] = 0.f;
-    }
-    for (int i = g; i < d.na; i += G) { ST_ST(a.s.act, (size_t)e * d.na + i, 0.f); if (ob) ob[o_act + i] = 0.f; }
-    if (g == 0) { a.s.time[e] = 0.f; if (a.s.status) a.s.status[e] = 0; ro.episode[e] = ep + 1; }
-    if constexpr (Engine<G, NVP, GEN, INTEG>::CARRY) { if (carry_row && g == 0) E.carry_row()[0] = 0.f; }   // a re-armed env carries nothing over
-  }
-  }   // !dup
-  if constexpr (Engine<G, NVP, GEN, INTEG>::TW) { if (two_wave) E.tw_signal(0, Engine<G, NVP, GEN, INTEG>::TW_DONE); }
+  constexpr int RPL = 1;
+#include "myosim_engine_kernel_body.inc"
 }
-
+#if !MM_F64
+// Two constraint rows per lane (Engine's RPL = 2): general-row models with 64 < njmax <= 128, one env per wave, Euler, fp32
+// (myosim_inst_list.hpp: MM_KERNELS_S).  A symbol of its own: k_engine's instantiations keep their names and their code.
+template <int NVP, bool LM>
+__global__ void __launch_bounds__(512) k_engine_rows2(KArgs a) {
+  constexpr int G = 64, INTEG = 0, RPL = 2;
+  constexpr bool GEN = true, OBS = false;
+#include "myosim_engine_kernel_body.inc"
+}
+#endif

@@ -12,6 +12,9 @@
 #define MM_KERNELS_H(X) X(64, 36, 1, 0)   /* leg models: 34 dofs (the 40-wide tile wastes 20 % of the dense linear algebra) */
 #define MM_KERNELS_I(X) X(64, 24, 1, 0)   /* row-rich models with <= 24 dofs (key turn, torso) */
 #define MM_KERNELS_J(X) X(4, 4, 0, 2) X(32, 24, 0, 2) X(64, 36, 1, 2)   /* implicitfast: elbow, hand, leg at their default widths */
+/* two constraint rows per lane (k_engine_rows2<NVP, LM>: 64 < njmax <= 128 at 64 lanes per env, Euler, fp32): the reorient family and
+   the dense-pair hand (32), the self-colliding hand / key turn / torso (24), the legs (36) */
+#define MM_KERNELS_S(X) X(64, 32, 1, 0) X(64, 24, 1, 0) X(64, 36, 1, 0)
 /* reset-observation pass as its own kernel (k_engine<..., OBS = true>, model through L2): the BASELINE workloads whose reset is not
    folded into the env-step launch -- reorient, leg-walk (Euler and implicitfast) */
 #define MM_KERNELS_OBS(X) X(64, 32, 1, 0) X(64, 36, 1, 0) X(64, 36, 1, 2)
@@ -32,3 +35,9 @@
   extern template __global__ void k_engine<G_, N_, false, GN_ != 0, RK_>(KArgs);
 #define MM_INSTANTIATE_OBS(G_, N_, GN_, RK_) template __global__ void k_engine<G_, N_, false, GN_ != 0, RK_, true>(KArgs);
 #define MM_DECLARE_OBS(G_, N_, GN_, RK_) extern template __global__ void k_engine<G_, N_, false, GN_ != 0, RK_, true>(KArgs);
+#define MM_INSTANTIATE_ROWS2(G_, N_, GN_, RK_)                    \
+  template __global__ void k_engine_rows2<N_, true>(KArgs);   \
+  template __global__ void k_engine_rows2<N_, false>(KArgs);
+#define MM_DECLARE_ROWS2(G_, N_, GN_, RK_)                               \
+  extern template __global__ void k_engine_rows2<N_, true>(KArgs);   \
+  extern template __global__ void k_engine_rows2<N_, false>(KArgs);

@@ -32,7 +32,8 @@ RWD_KEYS_REORIENT = ["pos_align", "rot_align", "act_reg", "drop", "bonus", "spar
 RWD_KEYS_WALK = ["vel_reward", "cyclic_hip", "ref_rot", "joint_angle_rew", "act_mag", "sparse", "solved", "done", "dense"]
 (INFO_NQ, INFO_NV, INFO_NU, INFO_NA, INFO_NBODY, INFO_NSITE, INFO_NTENDON, INFO_LANES, INFO_LDS_PER_ENV,
  INFO_ENVS_PER_BLOCK, INFO_NGEOM, INFO_WAVES_PER_BLOCK, INFO_KERNEL_FAMILY, INFO_MODEL_WORDS,
- INFO_BODY_CHAINS, INFO_FOLDED_RESET, INFO_FWD_CARRY, INFO_TENDON_ITEMS, INFO_TENDON_FOLDED) = range(19)
+ INFO_BODY_CHAINS, INFO_FOLDED_RESET, INFO_FWD_CARRY, INFO_TENDON_ITEMS, INFO_TENDON_FOLDED, INFO_EFC_ROWS) = range(20)
+MM_MAX_EFC_ROWS = 128   # include/myosim.h: most constraint rows (njmax) of a general-row model
 
 
 MM_ABI_VERSION = 7   # include/myosim.h
@@ -82,6 +83,8 @@ FILE_FLAGS = {"myosim_inst_B.hip": ["-mllvm", "-sink-insts-to-avoid-spills=1", "
               # +0.9 % (1.690 -> 1.705 M in one session).  Round 3 had measured -1 % for it on this unit, at 26 spills and no carry.
               # (incremental Newton measured +2.3 % here -- and 45 spilled VGPRs: off, this unit stays at zero)
               "myosim_inst_J.hip": ["-mllvm", "-sink-insts-to-avoid-spills=1"],
+              # two-rows-per-lane kernels (64 < njmax <= 128): as the one-row units of the same widths (inst_D / H / I)
+              "myosim_inst_S.hip": ["-mllvm", "-sink-insts-to-avoid-spills=1"],
               # precision-mode (fp64) kernels: IEEE divide / sqrt and no reassociation -- these exist to track the fp64 reference;
               # fma contraction stays on (it only removes roundings)
               "myosim_inst_P.hip": ["-fno-fast-math", "-ffp-contract=fast"],

@@ -960,6 +960,18 @@ def make_hand_dense() -> ModelSpec:
     return s
 
 
+def make_hand_dense_full() -> ModelSpec:
+    """`hand_dense` with the contact / row bounds raised to what the two-rows-per-lane kernels hold (njmax 128; nconmax 26: the 23
+    limit rows + 26 condim-3 contacts = 127 rows), so that a contact `mj_collision` keeps is not dropped for want of a row: the same
+    189 pairs, the same everything else.  How many of them a rollout needs: tests/tools/rows128_oracle_bounds.py (the parity scan's
+    stream peaks at 11 contacts / 52 rows: tests/test_rows128.py)."""
+    s = make_hand_dense()
+    s.name = "myohand_dense_full"
+    s.nconmax = 26
+    s.njmax = 128
+    return s
+
+
 # ----------------------------------------------------------------------------- contact toy
 def make_contact_toy() -> ModelSpec:
     """Small model that exercises every contact primitive of the engine (plane-sphere, plane-capsule,
@@ -1141,7 +1153,7 @@ def builders() -> dict:
             "motorfinger": lambda: make_finger(motor=True), "torso": make_torso,
             "friction_toy": make_friction_toy, "hand_keyturn": make_hand_keyturn,
             "tendon_limit_toy": make_tendon_limit_toy, "hand_contact": lambda: make_hand(self_collision=True),
-            "hand_dense": make_hand_dense,
+            "hand_dense": make_hand_dense, "hand_dense_full": make_hand_dense_full,
             "leg_implicit": lambda: make_leg(implicit=True), "torso_exo": lambda: make_torso(exosuit=True),
             "tree_star": lambda: make_tree_toy("star"), "tree_chain": lambda: make_tree_toy("chain"),
             "tree_comb": lambda: make_tree_toy("comb"), "tree_free": lambda: make_tree_toy("free"), "plane_toy": make_plane_toy}
