@@ -410,6 +410,10 @@ int  mm_uniform(float* out, size_t n, uint64_t seed, uint64_t stream_id, void* s
  * global [nenv_total][nu] action matrix: first_index = env_index_base * nu) */
 int  mm_uniform_at(float* out, size_t n, uint64_t seed, uint64_t stream_id, size_t first_index, void* stream);
 
+/* test hook: the device image of a model -- its words [0, MM_INFO_MODEL_WORDS) and behind them the two constant blocks (one-wave /
+ * two-wave launches) -- copied back into out[0 .. cap_words).  Returns the word count; MM_EARG when cap_words is too small. */
+int  mm_debug_model_image(const mm_model* m, uint32_t* out, int cap_words);
+
 const char* mm_last_error(void);
 const char* mm_version(void);
 int  mm_abi_version(void);                 /* MM_ABI_VERSION of the header the library was compiled from */

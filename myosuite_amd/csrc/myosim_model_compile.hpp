@@ -1,0 +1,776 @@
+#pragma once
+// myosim_model_compile.hpp -- the host-only model compiler: model blob (include/myosim_model.h) -> ModelImage, everything a model's
+// kernels read besides state.  Standard library only (no HIP): mm_model_create (myosim_engine.hip) uploads the image, and a plain
+// host build (tests/tools/model_image_main.cpp) runs the same code under the host sanitizers.
+//
+// compile_model (at the end) runs one function per job; DESIGN.md section 4 lists them in order.
+#include <math.h>
+#include <string.h>
+#include <algorithm>
+#include <array>
+#include <string>
+#include <vector>
+
+#include "myosim_engine_types.hpp"
+#include "myosim_inst_list.hpp"
+
+#ifndef MM_SPARSE_LDL
+#define MM_SPARSE_LDL 1   /* 0: dense register Cholesky in every kernel -- the dense fallback (myosim_engine_body.inc) */
+#endif
+#ifndef MM_ENV_SKEW
+#define MM_ENV_SKEW 1
+#endif
+
+// what mm_model holds besides its device pointer and launch options
+struct ModelImage {
+  std::vector<uint32_t> words;   // the device image: model blob, engine-private tables (Aux), then the two ConstBlocks
+  int sec[MM_NSEC];
+  Dims d;
+  Layout L, Ltw;   // LDS tables of an env in a one-wave / two-wave launch (env_layout)
+  DbgLayout D;
+  Aux x;
+  int lanes = 64;
+  int lanes_auto = 1;        // pick the group width per launch from the batch size
+  int nvp = 24;
+  int rpl = 1;               // constraint rows per lane of the general-row kernels: 2 for 64 < njmax <= 128 (k_engine_rows2, 64 lanes per env)
+  int precision = MM_PREC_F32;   // MM_PREC_*: which kernel family steps this model (mm_model_set_option "precision")
+  int blob_words = 0;
+  int cofs = 0, cofs_tw = 0; // word offsets of the ConstBlocks (one-wave / two-wave launches) behind the model words
+  size_t lds_per_env = 0, lds_per_env_tw = 0;   // bytes of LDS tables per env (one-wave / two-wave launches)
+  float origin[3] = {0.f, 0.f, 0.f};   // internal world-frame origin (see Dims::ox)
+  int nseg = 0;                             // segments of the dof tree (SP kernels)
+  int nwrapitem = 0;                        // tendon path items that wrap a geom (tangent points kept in LDS)
+  std::vector<double> ten_len0;             // per tendon: summed length of its path segments between rigidly connected bodies (folded at create)
+  std::vector<uint8_t> baked_body;          // bodies whose frame position such a folded segment spans (a per-env body_pos on one is refused)
+  int nfolded = 0;                          // path items folded into ten_len0
+};
+
+static const int kNvpChoices[] = {4, 24, 32, 36, 40};
+static const int kConstWords = (int)((sizeof(ConstBlock) + 3) / 4);
+// integrator -> kernel variant (template argument INTEG)
+static inline int integ_kernel(int integrator) { return integrator == MM_INT_RK4 ? 1 : (integrator == MM_INT_IMPLICITFAST ? 2 : 0); }
+
+#define MM_LISTED_(G_, N_, GN_, RK_) if (G == G_ && nvp == N_ && gen == GN_ && rk4 == RK_) return true;
+// is (lanes_per_env, padded nv, general-rows, integrator) a compiled instantiation?  (myosim_inst_list.hpp)
+// rpl = 2: of the two-rows-per-lane kernels (MM_KERNELS_S)
+static inline bool have_kernel(int G, int nvp, int gen, int rk4 = 0, int rpl = 1) {
+  if (rpl == 2) { MM_KERNELS_S(MM_LISTED_) return false; }
+  MM_KERNEL_LIST(MM_LISTED_)
+  return false;
+}
+// ... and of the precision-mode family (mm64::k_engine; myosim_inst_list.hpp: MM_KERNELS_F64)
+static inline bool have_kernel_f64(int G, int nvp, int gen, int rk4) {
+  MM_KERNELS_F64(MM_LISTED_)
+  return false;
+}
+// ... and of the reset-observation kernels (MM_KERNELS_OBS)
+static inline bool have_obs_kernel(int G, int nvp, int gen, int rk4) {
+  MM_KERNELS_OBS(MM_LISTED_)
+  return false;
+}
+#undef MM_LISTED_
+// the check every width decision goes through: a compiled instantiation of the model's kernel family
+static inline bool have_model_kernel(const ModelImage* m, int G) {
+  const int rk = integ_kernel(m->d.integrator);
+  if (m->precision != MM_PREC_F32) return m->rpl == 1 && have_kernel_f64(G, m->nvp, m->d.gen, rk);
+  return have_kernel(G, m->nvp, m->d.gen, rk, m->rpl);
+}
+
+// LDS tables of one env.  two_wave: the layout of a launch that gives every env a helper wave (Engine::TW): tables that share words
+// in a one-wave launch because ONE wave never needs both at a time (joint anchors / axes vs the composite inertias, the tendons'
+// tangent points vs the u1 scratch) get their own words, plus a second dense tile and the meeting counters.
+static inline Layout env_layout(const ModelImage* m, bool two_wave) {
+  const Dims& d = m->d;
+  Layout L;
+  memset(&L, 0, sizeof(L));
+  int o = 0;
+  auto take = [&](int n) { int r = o; o += (n > 0 ? n : 0); return r; };
+  L.qpos = take(d.nq); L.qvel = take(d.nv); L.act = take(d.na); L.ctrl = take(d.nu); L.actdot = take(d.na);
+  L.xpos = take(3 * d.nbody); L.xmat = take(9 * d.nbody);
+  L.com = take(3 * m->x.nroot); L.cdof = take(6 * d.nv);
+  o = (o + 3) & ~3;
+  // 12 words (cvel, cacc) + 1 pointer-jumping word per body | dense tile | SP kernels: published rows [nvp][12], x [nvp], update
+  // matrices [nseg][36]
+  // row stride of the dense tile(s): Engine::TD (the 32-wide tile of the dense kernels is padded against LDS bank conflicts)
+  const bool sp_kernel = MM_SPARSE_LDL && !d.gen && m->nvp >= 8 && d.integrator != MM_INT_IMPLICITFAST;
+  const int td = (!sp_kernel && m->nvp == 32) ? 36 : m->nvp;
+  const int u1_words = std::max(std::max(14 * d.nbody, m->nvp * td), d.seg_u + 36 * m->nseg);   // (CVS + 1) * nbody: Engine::CVS
+  L.u1 = take(u1_words);
+  if (two_wave) { L.crb = take(10 * d.nbody); L.xanchor = take(3 * d.njnt); L.xaxis = take(3 * d.njnt); }
+  else { L.crb = take(std::max(10 * d.nbody, 6 * d.njnt)); L.xanchor = L.crb; L.xaxis = L.crb + 3 * d.njnt; }   // anchors / axes die before crb
+  L.tenlen = take(d.ntendon); L.tenvel = take(d.ntendon); L.tenj = take(d.ntenJ); L.tenfrc = take(d.ntendon);
+  L.wrapw = (!two_wave && 7 * m->nwrapitem <= u1_words) ? L.u1 : take(7 * m->nwrapitem);   // u1 is free between FK and the velocity stage
+  L.flags = take(two_wave ? 4 : 0);
+  L.actlen = take(d.nu); L.actvel = take(d.nu); L.actfrc = take(d.nu);
+  L.vec = take(d.nv);
+  o = (o + 3) & ~3;
+  L.xvec = take(m->nvp);
+  if (d.integrator == MM_INT_RK4) { L.rk_qpos0 = take(d.nq); L.rk_act0 = take(d.na); L.rk_adot = take(d.na); }
+  if (d.integrator == MM_INT_IMPLICITFAST) { L.tenw = take(d.ntendon); L.dofw = take(d.nv); }
+  if (d.gen) { o = (o + 3) & ~3; L.efcJ = take(d.efc_rows * (m->nvp + 4)); L.rowtab = take(3 * m->rpl * m->lanes); }
+  if (two_wave) { o = (o + 3) & ~3; L.mtile = take(m->nvp * td + m->nvp); }
+  // 16-byte aligned env stride (wide ds_read/ds_write never straddle), skewed by 4 words so that neighbouring
+  // envs of a wave do not start on the same LDS bank
+  o = (o + 3) & ~3;
+  if (MM_ENV_SKEW && m->nvp <= 4) {
+    // tiny models run 4 .. 16 envs per wave (8 lanes per env for the elbow at 4096 envs): a ds_read_b32 is serviced in groups of
+    // 32 lanes over 32 banks, i.e. four 8-lane envs at a time -- an env stride of 8 (mod 32) words puts their same-offset
+    // accesses on disjoint banks (rocprofv3: 32 % of the elbow kernel's LDS cycles were conflict cycles with the old skew of 4)
+    while ((o & 31) != 8) o += 4;
+  } else if ((o & 31) == 0) o += 4;
+  L.total = o;
+  return L;
+}
+static inline void build_layout(ModelImage* m) {
+  m->d.efc_rows = std::min(m->rpl * m->lanes, (m->d.njmax + 3) & ~3);
+  m->d.seg_u = 13 * m->nvp;
+  const Dims& d = m->d;
+  m->L = env_layout(m, false);
+  m->Ltw = env_layout(m, true);
+  const size_t word = m->precision != MM_PREC_F32 ? 8 : 4;   // the tables hold `real`: precision mode doubles them
+  m->lds_per_env = (size_t)m->L.total * word;
+  m->lds_per_env_tw = (size_t)m->Ltw.total * word;
+  int o = 0;
+  auto take = [&](int n) { int r = o; o += (n > 0 ? n : 0); return r; };
+  DbgLayout& D = m->D;
+  D.xpos = take(3 * d.nbody); D.xquat = take(4 * d.nbody); D.xipos = take(3 * d.nbody); D.cdof = take(6 * d.nv);
+  D.cvel = take(6 * d.nbody); D.tenlen = take(d.ntendon); D.tenvel = take(d.ntendon); D.tenj = take(d.ntenJ);
+  D.actfrc = take(d.nu); D.actdot = take(d.na); D.M = take(d.nv * d.nv); D.bias = take(d.nv); D.smooth = take(d.nv);
+  D.qaccsm = take(d.nv); D.qacc = take(d.nv); D.qfrccon = take(d.nv);
+  D.efc_active = take(64); D.efc_D = take(64); D.efc_aref = take(64); D.scal = take(32 + 64);   // (+ 64: per-iteration Newton trace of a MM_NEWTON_TRACE tools build)
+  D.total = o;
+}
+// dims / LDS layout / aux offsets as the kernel reads them: the ConstBlocks of one-wave and two-wave launches (the same dims and
+// tables, the other LDS layout) at the tail of the image; re-written when the layout or an option changes
+static inline void write_consts(ModelImage* m) {
+  ConstBlock cb;
+  memset(&cb, 0, sizeof(cb));
+  cb.d = m->d; cb.L = m->L; cb.x = m->x;
+  memcpy(&m->words[m->cofs], &cb, sizeof(cb));
+  cb.L = m->Ltw;
+  memcpy(&m->words[m->cofs_tw], &cb, sizeof(cb));
+}
+
+static inline int check_lanes(const ModelImage* m, int lanes) {
+  const Dims& d = m->d;
+  if (lanes != 4 && lanes != 8 && lanes != 16 && lanes != 32 && lanes != 64) return 0;
+  if (d.nbody > lanes || d.nv > lanes || d.njnt > lanes || m->nvp > lanes) return 0;
+  // one constraint row (two with m->rpl = 2: one env per wave only) / one equality per lane; the explicit pair list is swept in chunks
+  // of `lanes` pairs (make_constraint_gen), bounded by MM_MAX_PAIRS (the pair index shares a row-descriptor word with the row kind)
+  if (d.gen && (d.njmax > m->rpl * lanes || d.neq > lanes || d.npair > MM_MAX_PAIRS)) return 0;
+  if (m->rpl == 2 && lanes != 64) return 0;
+  return 1;
+}
+
+namespace mmc {   // the jobs of compile_model
+
+static inline int refuse(std::string& err, int code, const char* msg) { err = msg; return code; }
+
+// read-only view of a model blob: typed section accessors (len: section lengths in words, not validated)
+struct BlobView {
+  const uint32_t* w;
+  int nwords;
+  int sec[MM_NSEC], len[MM_NSEC];
+  const int32_t* i(int s) const { return reinterpret_cast<const int32_t*>(w + sec[s]); }
+  const float* f(int s) const { return reinterpret_cast<const float*>(w + sec[s]); }
+  const uint32_t* u(int s) const { return w + sec[s]; }
+};
+
+static inline int open_blob(const uint32_t* blob, int nwords, BlobView& b, std::string& err) {
+  if (!blob || nwords < MM_HEADER_WORDS + 2 * MM_NSEC) return refuse(err, MM_EBADBLOB, "blob too short");
+  if (blob[0] != MM_MAGIC || blob[1] != MM_VERSION || blob[2] != MM_NSEC || (int)blob[3] != nwords)
+    return refuse(err, MM_EBADBLOB, "bad magic/version/section count");
+  b.w = blob; b.nwords = nwords;
+  for (int s = 0; s < MM_NSEC; s++) { b.sec[s] = (int)blob[MM_HEADER_WORDS + 2 * s]; b.len[s] = (int)blob[MM_HEADER_WORDS + 2 * s + 1]; }
+  return MM_OK;
+}
+
+// Dims from the option sections, the row counts and the kernel family they select
+static inline int read_dims(const BlobView& b, Dims& d, std::string& err) {
+  const int32_t *oi = b.i(MM_SEC_OPT_I);
+  const float *of = b.f(MM_SEC_OPT_F);
+  d.nq = oi[MM_OI_NQ]; d.nv = oi[MM_OI_NV]; d.nu = oi[MM_OI_NU]; d.na = oi[MM_OI_NA]; d.nbody = oi[MM_OI_NBODY];
+  d.njnt = oi[MM_OI_NJNT]; d.ngeom = oi[MM_OI_NGEOM]; d.nsite = oi[MM_OI_NSITE]; d.ntendon = oi[MM_OI_NTENDON];
+  d.nwrap = oi[MM_OI_NWRAP]; d.neq = oi[MM_OI_NEQ]; d.npair = oi[MM_OI_NPAIR]; d.nM = oi[MM_OI_NM];
+  d.nlevel = oi[MM_OI_NLEVEL]; d.njmax = oi[MM_OI_NJMAX]; d.nconmax = oi[MM_OI_NCONMAX]; d.ntenJ = oi[MM_OI_NTENJ];
+  d.condim4 = 0;     // set by check_rows when a pair carries condim 4
+  d.iterations = oi[MM_OI_ITERATIONS]; d.ls_iterations = oi[MM_OI_LS_ITERATIONS]; d.eulerdamp = oi[MM_OI_EULERDAMP];
+  d.timestep = of[MM_OF_TIMESTEP]; d.gx = of[MM_OF_GRAV_X]; d.gy = of[MM_OF_GRAV_Y]; d.gz = of[MM_OF_GRAV_Z];
+  d.tolerance = of[MM_OF_TOLERANCE]; d.ls_tolerance = of[MM_OF_LS_TOLERANCE]; d.meaninertia = of[MM_OF_MEANINERTIA];
+  d.integrator = oi[MM_OI_INTEGRATOR];
+  if (d.integrator != MM_INT_EULER && d.integrator != MM_INT_RK4 && d.integrator != MM_INT_IMPLICITFAST)
+    return refuse(err, MM_EUNSUPPORTED, "integrator must be Euler (0), RK4 (1) or implicitfast (3)");
+  d.ntlim = 0;
+  const int32_t *tlim = b.i(MM_SEC_TENDON_LIMITED);
+  const float *trng = b.f(MM_SEC_TENDON_RANGE), *tmar = b.f(MM_SEC_TENDON_MARGIN);
+  for (int t = 0; t < d.ntendon; t++) {
+    if (!tlim[t]) continue;
+    d.ntlim++;
+    if (trng[2 * t + 1] - trng[2 * t] < 2.f * tmar[t]) return refuse(err, MM_EUNSUPPORTED, "tendon range narrower than 2*margin");
+  }
+  d.nfric = 0;
+  const float *fl = b.f(MM_SEC_DOF_FRICTIONLOSS);
+  for (int i = 0; i < d.nv; i++) if (fl[i] > 0.f) d.nfric++;
+  int nlimjnt = 0;     // limited hinge / slide joints: the limit-rows-only kernel makes one row for each, it never reads njmax
+  const int32_t *jt = b.i(MM_SEC_JNT_TYPE), *jl = b.i(MM_SEC_JNT_LIMITED);
+  for (int j = 0; j < d.njnt; j++) if (jl[j] && (jt[j] == MM_JNT_HINGE || jt[j] == MM_JNT_SLIDE)) nlimjnt++;
+  // (an explicit njmax below the limit count takes the general-row kernel, which drops the rows beyond it as the oracle does; the
+  // derived njmax counts every limit, so no shipped model changes family)
+  d.gen = (d.neq > 0 || d.npair > 0 || d.nfric > 0 || d.ntlim > 0 || d.njmax < nlimjnt) ? 1 : 0;
+  return MM_OK;
+}
+
+// Tables of the tree-sparse factorisation (Engine::sp_factor_solve / sp_mul_m): depth of every dof, its descendants, its ancestors,
+// and the SEGMENTS of the dof tree (maximal unbranched chains; a dof starts a segment when its parent has another child too).
+// The limit-rows-only kernels keep M tree-sparse with at most 8 entries per row (dof + 7 ancestors); a tree that does not fit
+// (deeper, or beyond a table limit) takes the general-row kernels, whose factorisations are dense: sets Dims::gen then.
+struct DofTree { std::vector<int32_t> desc, seg, anc; int nseg = 0; };   // Aux::dof_desc / dof_seg / dof_anc
+static inline DofTree build_dof_tree(const BlobView& b, Dims& d) {
+  DofTree T;
+  const int32_t *dpar = b.i(MM_SEC_DOF_PARENTID);
+  int maxd = 0;
+  for (int i = 0; i < d.nv; i++) {
+    int dep = 0;
+    for (int j = dpar[i]; j >= 0; j = dpar[j]) dep++;
+    if (dep > maxd) maxd = dep;
+  }
+  d.dof_nlevel = maxd + 1;
+  std::vector<int> dep(d.nv, 0), nchild(d.nv, 0);
+  for (int i = 0; i < d.nv; i++) { dep[i] = dpar[i] < 0 ? 0 : dep[dpar[i]] + 1; if (dpar[i] >= 0) nchild[dpar[i]]++; }
+  bool fits = d.dof_nlevel <= 8 && d.nv < 255;
+  const size_t nvs = (size_t)(d.nv > 0 ? d.nv : 1);
+  T.desc.assign(nvs * 8, -1);
+  T.seg.assign(nvs * 6, -1);
+  for (int i = 0; i < d.nv; i++) T.seg[(size_t)i * 6 + 5] = dep[i];
+  T.anc.assign(nvs * 2, 0);
+  for (int i = 0; i < d.nv && fits; i++)
+    for (int k = dpar[i]; k >= 0; k = dpar[k]) T.anc[(size_t)i * 2 + (dep[k] >> 2)] |= (int32_t)((uint32_t)k << (8 * (dep[k] & 3)));
+  d.seg_nlevel = 0; d.seg_lvinfo[0] = d.seg_lvinfo[1] = 0; d.seg_lvtb[0] = d.seg_lvtb[1] = 0; d.seg_zero = 0; d.desc_words = 0;
+  if (fits) {
+    std::vector<int> ndesc(d.nv, 0);
+    for (int k = 0; k < d.nv && fits; k++)
+      for (int i = dpar[k]; i >= 0; i = dpar[i]) {
+        const int c = ndesc[i]++;
+        if (c >= 32) { fits = false; break; }
+        uint32_t w;
+        memcpy(&w, &T.desc[(size_t)i * 8 + (c >> 2)], 4);
+        w = (w & ~(255u << (8 * (c & 3)))) | ((uint32_t)k << (8 * (c & 3)));
+        memcpy(&T.desc[(size_t)i * 8 + (c >> 2)], &w, 4);
+        d.desc_words = std::max(d.desc_words, (c >> 2) + 1);
+      }
+  }
+  if (fits) {
+    struct Seg { int top, bottom, parent, level, nch; int ch[8]; };
+    std::vector<Seg> segs;
+    std::vector<int> seg_of(d.nv, -1);
+    for (int k = 0; k < d.nv && fits; k++) {
+      if (dpar[k] >= 0 && nchild[dpar[k]] == 1) { seg_of[k] = seg_of[dpar[k]]; segs[seg_of[k]].bottom = k; continue; }
+      Seg sg{}; sg.top = sg.bottom = k; sg.parent = dpar[k] >= 0 ? seg_of[dpar[k]] : -1;
+      sg.level = sg.parent >= 0 ? segs[sg.parent].level + 1 : 0;
+      if (sg.parent >= 0) {
+        Seg& ps = segs[sg.parent];
+        if (ps.nch >= 8) { fits = false; break; }
+        ps.ch[ps.nch++] = (int)segs.size();
+      }
+      seg_of[k] = (int)segs.size();
+      segs.push_back(sg);
+    }
+    if (segs.size() > 255) fits = false;
+    if (fits) {
+      // elimination steps: the kernel's segment code is scalar in (t, b), so the segments of one step must be alike: a step is
+      // a group (tree level, t, b); children sit at a deeper level, i.e. in a later step, and are eliminated first
+      std::vector<std::array<int, 3>> groups;
+      for (const Seg& sg : segs) {
+        std::array<int, 3> k{sg.level, dep[sg.top], dep[sg.bottom]};
+        if (std::find(groups.begin(), groups.end(), k) == groups.end()) groups.push_back(k);
+      }
+      std::sort(groups.begin(), groups.end());
+      if (groups.size() > 8) fits = false;
+      int mch[8] = {0};
+      for (size_t si = 0; si < segs.size() && fits; si++) {
+        const Seg& sg = segs[si];
+        const int t = dep[sg.top], bt = dep[sg.bottom];
+        const int step = (int)(std::find(groups.begin(), groups.end(), std::array<int, 3>{sg.level, t, bt}) - groups.begin());
+        mch[step] = std::max(mch[step], sg.nch);
+        uint32_t path[2] = {0, 0}, ch[2] = {0xffffffffu, 0xffffffffu};
+        for (int k = sg.bottom; k >= 0; k = dpar[k]) path[dep[k] >> 2] |= (uint32_t)k << (8 * (dep[k] & 3));
+        for (int c = 0; c < sg.nch; c++) ch[c >> 2] = (ch[c >> 2] & ~(255u << (8 * (c & 3)))) | ((uint32_t)sg.ch[c] << (8 * (c & 3)));
+        int32_t* e = &T.seg[(size_t)sg.top * 6];
+        e[0] = t | (bt << 4) | (step << 8) | ((int)si << 16);
+        e[1] = (int32_t)path[0]; e[2] = (int32_t)path[1]; e[3] = (int32_t)ch[0]; e[4] = (int32_t)ch[1];
+      }
+      d.seg_lvtb[0] = d.seg_lvtb[1] = 0;
+      if (fits) {
+        d.seg_nlevel = (int)groups.size();
+        for (size_t l = 0; l < groups.size(); l++) {
+          d.seg_lvinfo[l >> 2] |= mch[l] << (8 * (l & 3));
+          d.seg_lvtb[l >> 2] |= (groups[l][1] | (groups[l][2] << 4)) << (8 * (l & 3));
+        }
+      }
+      T.nseg = (int)segs.size() + 1;   // + the all-zero slot
+      d.seg_zero = (int)segs.size();
+    }
+  }
+  if (!fits) { d.seg_nlevel = 0; T.nseg = 0; }
+  if (!d.gen && d.nv > 4 && !fits && d.integrator != MM_INT_IMPLICITFAST) d.gen = 1;
+  return T;
+}
+
+// what the row builders of the kernels implement: joint equalities, the contact-pair table, joint ranges; then the dense tile
+static inline int check_rows(const BlobView& b, Dims& d, int& nvp, std::string& err) {
+  const int32_t *et = b.i(MM_SEC_EQ_TYPE);
+  for (int e = 0; e < d.neq; e++)
+    if (et[e] != MM_EQ_JOINT) return refuse(err, MM_EUNSUPPORTED, "only joint equalities are implemented");
+  const int32_t *gt = b.i(MM_SEC_GEOM_TYPE), *p1 = b.i(MM_SEC_PAIR_GEOM1), *p2 = b.i(MM_SEC_PAIR_GEOM2), *pc = b.i(MM_SEC_PAIR_CONDIM);
+  for (int p = 0; p < d.npair; p++) {
+    const int t1 = gt[p1[p]], t2 = gt[p2[p]];
+    const bool ok = (t1 == MM_GEOM_PLANE && (t2 == MM_GEOM_SPHERE || t2 == MM_GEOM_CAPSULE || t2 == MM_GEOM_ELLIPSOID || t2 == MM_GEOM_CYLINDER || t2 == MM_GEOM_BOX)) ||
+                    (t1 == MM_GEOM_SPHERE && (t2 == MM_GEOM_SPHERE || t2 == MM_GEOM_CAPSULE || t2 == MM_GEOM_ELLIPSOID || t2 == MM_GEOM_CYLINDER || t2 == MM_GEOM_BOX)) ||
+                    (t1 == MM_GEOM_CAPSULE && (t2 == MM_GEOM_CAPSULE || t2 == MM_GEOM_ELLIPSOID || t2 == MM_GEOM_CYLINDER || t2 == MM_GEOM_BOX));
+    if (t1 == MM_GEOM_PLANE && (t2 == MM_GEOM_CYLINDER || t2 == MM_GEOM_BOX)) {
+      // up to four contacts: two consecutive identical entries, two contacts each (include/myosim_model.h, PAIR_* sections)
+      const bool twin = (p > 0 && p1[p - 1] == p1[p] && p2[p - 1] == p2[p]) || (p + 1 < d.npair && p1[p + 1] == p1[p] && p2[p + 1] == p2[p]);
+      if (!twin) return refuse(err, MM_EBADBLOB, "a plane-box / plane-cylinder pair takes two consecutive entries of the PAIR_* sections");
+    }
+    if (!ok) return refuse(err, MM_EUNSUPPORTED, "contact pair types: plane vs sphere/capsule/ellipsoid/cylinder/box, sphere/capsule among themselves, sphere/capsule vs ellipsoid/cylinder/box (geom1 type <= geom2 type)");
+    if (pc[p] == 4) d.condim4 = 1;
+    if (pc[p] != 1 && pc[p] != 3 && pc[p] != 4) return refuse(err, MM_EUNSUPPORTED, "contact condim must be 1, 3 or 4 (pyramidal cone: 1 / 4 / 6 rows; rolling friction, condim 6, is not implemented)");
+  }
+  if (d.nv > 255) return refuse(err, MM_EUNSUPPORTED, "nv > 255");
+  const int32_t *jlim = b.i(MM_SEC_JNT_LIMITED);
+  const float *jr = b.f(MM_SEC_JNT_RANGE), *jm = b.f(MM_SEC_JNT_MARGIN);
+  for (int j = 0; j < d.njnt; j++)
+    if (jlim[j] && jr[2 * j + 1] - jr[2 * j] < 2.f * jm[j]) return refuse(err, MM_EUNSUPPORTED, "joint range narrower than 2*margin");
+  const float *damp = b.f(MM_SEC_DOF_DAMPING);
+  d.any_damping = 0;
+  for (int i = 0; i < d.nv; i++) if (damp[i] > 0.f) d.any_damping = 1;
+  nvp = 0;
+  for (int c : kNvpChoices) if (d.nv <= c) { nvp = c; break; }
+  if (!nvp) return refuse(err, MM_EUNSUPPORTED, "nv larger than the largest compiled dense tile (40)");
+  return MM_OK;
+}
+
+struct BodyTables { std::vector<int32_t> depth, roots, rootslot, dofslot; };
+static inline BodyTables body_tables(const BlobView& b, const Dims& d) {
+  const int32_t *bpar = b.i(MM_SEC_BODY_PARENT), *brootid = b.i(MM_SEC_BODY_ROOTID), *dofbody = b.i(MM_SEC_DOF_BODYID);
+  BodyTables B;
+  B.depth.assign(d.nbody, 0); B.rootslot.assign(d.nbody, 0); B.dofslot.assign(d.nv, 0);
+  for (int k = 1; k < d.nbody; k++) B.depth[k] = B.depth[bpar[k]] + 1;
+  for (int k = 1; k < d.nbody; k++) if (bpar[k] == 0) B.roots.push_back(k);
+  for (int k = 1; k < d.nbody; k++)
+    for (size_t r = 0; r < B.roots.size(); r++) if (B.roots[r] == brootid[k]) B.rootslot[k] = (int)r;
+  for (int i = 0; i < d.nv; i++) B.dofslot[i] = B.rootslot[dofbody[i]];
+  return B;
+}
+
+// The three sums below are evaluated in a fixed order (host code is built with -ffast-math, which otherwise lets the compiler
+// reassociate a sum by the code around it): the order the recorded images hold to the last bit (tests/test_model_image.py).
+// rotation matrix (row major) of a unit quaternion (w, x, y, z)
+static inline void quat_to_mat(const double* q, double R[9]) {
+#pragma clang fp reassociate(off)
+  const double w = q[0], x = q[1], y = q[2], z = q[3];
+  R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - w * z); R[2] = 2 * (x * z + w * y);
+  R[3] = 2 * (x * y + w * z); R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - w * x);
+  R[6] = 2 * (x * z - w * y); R[7] = 2 * (y * z + w * x); R[8] = 1 - 2 * (x * x + y * y);
+}
+// frame position + R * local (a float[3] of the blob); last: which of the three products is added last (2: in reading order)
+static inline void frame_point(const double* xp, const double R[9], const float* v, double out[3], int last = 2) {
+#pragma clang fp reassociate(off)
+  const int mid = 3 - last;
+  for (int k = 0; k < 3; k++) out[k] = ((xp[k] + R[3 * k] * (double)v[0]) + R[3 * k + mid] * (double)v[mid]) + R[3 * k + last] * (double)v[last];
+}
+// distance of two points
+static inline double point_distance(const double* p0, const double* p1) {
+#pragma clang fp reassociate(off)
+  const double dx = p1[0] - p0[0], dy = p1[1] - p0[1], dz = p1[2] - p0[2];
+  return std::sqrt((dy * dy + dz * dz) + dx * dx);
+}
+
+// body frames of the reference configuration (joints at their reference values: the relative pose of two bodies that no dof
+// separates does not depend on the configuration)
+struct RefFrames { std::vector<double> xp, xq; };
+static inline RefFrames reference_frames(const BlobView& b, const Dims& d) {
+  const int32_t *bpar = b.i(MM_SEC_BODY_PARENT);
+  const float *bpos = b.f(MM_SEC_BODY_POS), *bquat = b.f(MM_SEC_BODY_QUAT);
+  RefFrames F;
+  F.xp.assign(3 * (size_t)std::max(d.nbody, 1), 0.0); F.xq.assign(4 * (size_t)std::max(d.nbody, 1), 0.0);
+  F.xq[0] = 1.0;
+  for (int k = 1; k < d.nbody; k++) {
+    const double* pq = &F.xq[4 * bpar[k]];
+    const double w = pq[0], x = pq[1], y = pq[2], z = pq[3];
+    double R[9];
+    quat_to_mat(pq, R);
+    frame_point(&F.xp[3 * bpar[k]], R, bpos + 3 * k, &F.xp[3 * k], 1);
+    const double a0 = bquat[4 * k], a1 = bquat[4 * k + 1], a2 = bquat[4 * k + 2], a3 = bquat[4 * k + 3];
+    double q[4] = {w * a0 - x * a1 - y * a2 - z * a3, w * a1 + x * a0 + y * a3 - z * a2,
+                   w * a2 - x * a3 + y * a0 + z * a1, w * a3 + x * a2 - y * a1 + z * a0};
+    const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    for (int c = 0; c < 4; c++) F.xq[4 * k + c] = n > 0 ? q[c] / n : (c == 0);
+  }
+  return F;
+}
+
+// internal world-frame origin (Dims::ox/oy/oz): mean body position of the reference configuration, on a 1/64 m grid.
+// Bodies hanging off a free joint start wherever qpos0 puts them, which body_pos already encodes.
+static inline void reference_origin(const RefFrames& F, const Dims& d, float origin[3]) {
+  double sum[3] = {0, 0, 0};
+  for (int k = 1; k < d.nbody; k++)
+    for (int c = 0; c < 3; c++) sum[c] += F.xp[3 * k + c];
+  const int nb1 = d.nbody > 1 ? d.nbody - 1 : 1;
+  for (int c = 0; c < 3; c++) origin[c] = (float)(std::round(64.0 * sum[c] / nb1) / 64.0);
+}
+
+// body of a path element (site / wrap geom), -1 for joints and pulleys
+static inline int elem_body(const BlobView& b, int k) {
+  const int32_t *wt = b.i(MM_SEC_WRAP_TYPE), *wo = b.i(MM_SEC_WRAP_OBJID);
+  if (wt[k] == MM_WRAP_SITE) return b.i(MM_SEC_SITE_BODYID)[wo[k]];
+  if (wt[k] == MM_WRAP_SPHERE || wt[k] == MM_WRAP_CYLINDER) return b.i(MM_SEC_GEOM_BODYID)[wo[k]];
+  return -1;
+}
+
+// Flattened path items (see Engine::tendon), 8 words each: wraps first, then straight segments, then fixed-tendon joint terms.
+// [tendon, kind (0 straight, 1 sphere wrap, 2 cylinder wrap, 3 joint), path element, site0 (kind 3: joint), site1 (kind 3: bits(coef)),
+// geom, sidesite, bits(1 / divisor)].  Rigid site-site segments are folded into m.ten_len0 / baked_body / nfolded instead.
+static inline std::vector<int32_t> tendon_path_items(const BlobView& b, const Dims& d, const RefFrames& F, ModelImage& m) {
+  const int32_t *bpar = b.i(MM_SEC_BODY_PARENT), *bdofnum = b.i(MM_SEC_BODY_DOFNUM), *wt = b.i(MM_SEC_WRAP_TYPE), *wo = b.i(MM_SEC_WRAP_OBJID);
+  const int32_t *tadr = b.i(MM_SEC_TENDON_ADR), *tnum = b.i(MM_SEC_TENDON_NUM), *sbody = b.i(MM_SEC_SITE_BODYID);
+  const float *spos = b.f(MM_SEC_SITE_POS), *wprm = b.f(MM_SEC_WRAP_PRM);
+  m.ten_len0.assign((size_t)std::max(d.ntendon, 1), 0.0);
+  m.baked_body.assign((size_t)std::max(d.nbody, 1), 0);
+  struct Item { int w[8]; };
+  std::vector<Item> wraps, straights, joints;
+  auto fbits = [](float f) { int32_t i; memcpy(&i, &f, 4); return i; };
+  for (int t = 0; t < d.ntendon; t++) {
+    int adr = tadr[t], num = tnum[t], j = 0;
+    float inv_div = 1.f;
+    for (int k = 0; k < num; k++)
+      if (wt[adr + k] == MM_WRAP_JOINT) joints.push_back(Item{{t, 3, adr + k, wo[adr + k], fbits(wprm[adr + k]), 0, 0, fbits(1.f)}});
+    while (j < num - 1) {
+      int t0 = wt[adr + j], t1 = wt[adr + j + 1];
+      if (t0 == MM_WRAP_JOINT) { j++; continue; }
+      if (t0 == MM_WRAP_PULLEY || t1 == MM_WRAP_PULLEY) {
+        if (t0 == MM_WRAP_PULLEY) inv_div = 1.f / wprm[adr + j];
+        j++;
+        continue;
+      }
+      const int k0 = adr + j;
+      if (t1 == MM_WRAP_SITE) {
+        // A straight segment between two sites whose bodies no dof separates (the same bone, or bones fixed to one another) has
+        // the same length in every pose and no Jacobian entry: it is summed into the tendon's constant here -- MyoSuite's muscle
+        // paths are mostly such via-point runs along a bone -- instead of being re-measured by a lane in every forward pass.
+        if (MM_FOLD_RIGID_SEGMENTS) {
+          int b0 = sbody[wo[k0]], b1 = sbody[wo[k0 + 1]];
+          std::vector<int> spanned;
+          bool rigid = true;
+          while (b0 != b1 && rigid) {
+            const int bb = b0 > b1 ? b0 : b1;
+            if (bdofnum[bb] > 0) rigid = false;
+            spanned.push_back(bb);
+            if (b0 > b1) b0 = bpar[b0]; else b1 = bpar[b1];
+          }
+          if (rigid) {
+            double p[2][3];
+            for (int e = 0; e < 2; e++) {
+              const int si = wo[k0 + e], sb = sbody[si];
+              double R[9];
+              quat_to_mat(&F.xq[4 * sb], R);
+              frame_point(&F.xp[3 * sb], R, spos + 3 * si, p[e]);
+            }
+            m.ten_len0[t] += point_distance(p[0], p[1]) * (double)inv_div;
+            for (int bb : spanned) m.baked_body[bb] = 1;
+            m.nfolded++;
+            j += 1;
+            continue;
+          }
+        }
+        straights.push_back(Item{{t, 0, k0, wo[k0], wo[k0 + 1], 0, -1, fbits(inv_div)}});
+        j += 1;
+      } else {
+        int side = (int)lrintf(wprm[k0 + 1]);
+        wraps.push_back(Item{{t, t1 == MM_WRAP_CYLINDER ? 2 : 1, k0, wo[k0], wo[k0 + 2], wo[k0 + 1], side, fbits(inv_div)}});
+        j += 2;
+      }
+    }
+  }
+  // spheres and cylinders apart, so that a sweep of lanes runs one wrap flavour
+  std::stable_sort(wraps.begin(), wraps.end(), [](const Item& x, const Item& y) { return x.w[1] > y.w[1]; });
+  std::vector<int32_t> item_tab;
+  for (auto* v : {&wraps, &straights, &joints})
+    for (const Item& it : *v) for (int k = 0; k < 8; k++) item_tab.push_back(it.w[k]);
+  m.nwrapitem = (int)wraps.size();
+  return item_tab;
+}
+
+// Tendon Jacobian by ENTRY (see Engine::tendon): every sparse-J entry (tendon, dof) gets the list of path segments that cross
+// its dof, one 4-word row per segment: S a site-site segment; a wrap item contributes its unwrapped segment A (site - site)
+// or, when the tendon touches the geom, B (site - tangent point) and / or C (tangent point - site): rows A_OR_B, A_OR_C (the
+// usual case: the dof lies between one site's body and the geom's body), B_ONLY, C_ONLY, A_ONLY; J a fixed-tendon coefficient;
+// NONE pads an entry nothing crosses.  Row: [entry | joint word << 16, site0 | site1 << 16, body0 | body1 << 8 | mode << 16 |
+// ep_unwrapped << 20 | ep_wrapped << 21 | wrap slot << 22, bits(1/divisor or coef)]; joint word = joint id | 1 (hinge) or
+// 2 (slide) << 8 -- the kernel reads anchor / axis straight from the joint -- or dof id for ball / free dofs (via cdof).
+// jent[i] = first row | rows << 24 of the i-th entry in processing order.
+static inline int tendon_jacobian_rows(const BlobView& b, const Dims& d, const std::vector<int32_t>& item_tab,
+                                       std::vector<int32_t>& jent, std::vector<int32_t>& jrow, std::string& err) {
+  const int32_t *bpar = b.i(MM_SEC_BODY_PARENT), *bdofadr = b.i(MM_SEC_BODY_DOFADR), *bdofnum = b.i(MM_SEC_BODY_DOFNUM);
+  const int32_t *tj_adr = b.i(MM_SEC_TENJ_ADR), *tj_dof = b.i(MM_SEC_TENJ_DOF), *sbody = b.i(MM_SEC_SITE_BODYID);
+  bool seg_ok = true;
+  auto entry_of = [&](int t, int dof) { int ent = -1; for (int e = tj_adr[t]; e < tj_adr[t + 1]; e++) if (tj_dof[e] == dof) ent = e; return ent; };
+  struct Cross { int ent, ep; };   // J entry a straight segment contributes to, and the end that moves with the dof
+  auto crossings = [&](int t, int b0, int b1) {
+    // dofs in chain(b0) XOR chain(b1): endpoint 0 for the b0 side (sign -), endpoint 1 for the b1 side (+)
+    std::vector<Cross> out;
+    while (b0 != b1) {
+      int bb, ep;
+      if (b0 > b1) { bb = b0; ep = 0; b0 = bpar[b0]; } else { bb = b1; ep = 1; b1 = bpar[b1]; }
+      for (int i = bdofadr[bb]; i >= 0 && i < bdofadr[bb] + bdofnum[bb]; i++) {
+        const int ent = entry_of(t, i);
+        if (ent < 0) { seg_ok = false; continue; }
+        out.push_back(Cross{ent, ep});
+      }
+    }
+    return out;
+  };
+  enum { R_S = 0, R_AB = 1, R_AC = 2, R_B = 3, R_C = 4, R_A = 5, R_J = 6, R_NONE = 7 };
+  struct Rec { int32_t sites, bm, wi, f2; };
+  std::vector<std::vector<Rec>> per_ent((size_t)d.ntenJ);
+  const int nit = (int)item_tab.size() / 8;
+  for (int ii = 0; ii < nit && seg_ok; ii++) {
+    const int32_t* I = &item_tab[8 * (size_t)ii];
+    const int t = I[0], kind = I[1], k0 = I[2];
+    if (kind == 3) {
+      const int ent = entry_of(t, b.i(MM_SEC_JNT_DOFADR)[I[3]]);
+      if (ent < 0) { seg_ok = false; break; }
+      per_ent[ent].push_back(Rec{0, R_J << 16, 0, I[4]});
+      continue;
+    }
+    if (I[3] >= 65536 || I[4] >= 65536 || sbody[I[3]] >= 256 || sbody[I[4]] >= 256) { seg_ok = false; break; }
+    const int32_t sites = I[3] | (I[4] << 16), bodies = sbody[I[3]] | (sbody[I[4]] << 8);
+    if (kind == 0) {
+      for (const Cross& c : crossings(t, elem_body(b, k0), elem_body(b, k0 + 1)))
+        per_ent[c.ent].push_back(Rec{sites, bodies | (R_S << 16) | (c.ep << 20), 0, I[7]});
+      continue;
+    }
+    const int b0 = elem_body(b, k0), b1 = elem_body(b, k0 + 1), b2 = elem_body(b, k0 + 2);
+    std::vector<Cross> ca = crossings(t, b0, b2), cb = crossings(t, b0, b1), cc = crossings(t, b1, b2);
+    auto take = [](std::vector<Cross>& v, int ent, int& ep) {
+      for (size_t k = 0; k < v.size(); k++) if (v[k].ent == ent) { ep = v[k].ep; v.erase(v.begin() + k); return true; }
+      return false;
+    };
+    for (const Cross& a_ : ca) {
+      int epw = 0;
+      if (take(cb, a_.ent, epw)) per_ent[a_.ent].push_back(Rec{sites, bodies | (R_AB << 16) | (a_.ep << 20) | (epw << 21), ii, I[7]});
+      else if (take(cc, a_.ent, epw)) per_ent[a_.ent].push_back(Rec{sites, bodies | (R_AC << 16) | (a_.ep << 20) | (epw << 21), ii, I[7]});
+      else per_ent[a_.ent].push_back(Rec{sites, bodies | (R_A << 16) | (a_.ep << 20), ii, I[7]});
+    }
+    for (const Cross& b_ : cb) per_ent[b_.ent].push_back(Rec{sites, bodies | (R_B << 16) | (b_.ep << 21), ii, I[7]});
+    for (const Cross& c_ : cc) per_ent[c_.ent].push_back(Rec{sites, bodies | (R_C << 16) | (c_.ep << 21), ii, I[7]});
+  }
+  if (!seg_ok) return refuse(err, MM_EUNSUPPORTED, "tendon Jacobian pattern in the blob does not cover a path segment");
+  // entries with the most rows first, then by the flavour of their first row: a sweep of lanes runs alike
+  std::vector<int> order((size_t)d.ntenJ);
+  for (int e = 0; e < d.ntenJ; e++) { order[e] = e; if (per_ent[e].empty()) per_ent[e].push_back(Rec{0, R_NONE << 16, 0, 0}); }
+  std::stable_sort(order.begin(), order.end(), [&](int x, int y) {
+    if (per_ent[x].size() != per_ent[y].size()) return per_ent[x].size() > per_ent[y].size();
+    return ((per_ent[x][0].bm >> 16) & 15) > ((per_ent[y][0].bm >> 16) & 15);
+  });
+  const int32_t *dofjnt = b.i(MM_SEC_DOF_JNTID), *jtype = b.i(MM_SEC_JNT_TYPE);
+  for (int e : order) {
+    const int dof = tj_dof[e], j = dofjnt[dof], ty = jtype[j];
+    const bool direct = (ty == MM_JNT_HINGE || ty == MM_JNT_SLIDE) && j < 256;
+    if ((!direct && dof >= 256) || e >= 65536 || per_ent[e].size() > 127 || jrow.size() / 4 >= (1u << 24))
+      return refuse(err, MM_EUNSUPPORTED, "tendon Jacobian beyond the engine's table limits");
+    const int32_t jw = (direct ? j : dof) | ((direct ? (ty == MM_JNT_HINGE ? 1 : 2) : 0) << 8);
+    jent.push_back((int32_t)(jrow.size() / 4) | ((int32_t)per_ent[e].size() << 24));
+    for (const Rec& r : per_ent[e]) {
+      if (r.wi >= 1024) return refuse(err, MM_EUNSUPPORTED, "more than 1024 wrapping tendon path items");
+      const int32_t row[4] = {e | (jw << 16), r.sites, r.bm | (r.wi << 22), r.f2};
+      for (int k = 0; k < 4; k++) jrow.push_back(row[k]);
+    }
+  }
+  return MM_OK;
+}
+
+// 4-word device rows of the path items: [tendon | kind << 16, site0 | site1 << 16 (kind 3: joint id), geom | (sidesite + 1) << 16
+// (kind 3: bits(coef)), bits(1 / divisor)]
+static inline int pack_path_items(const std::vector<int32_t>& item_tab, std::vector<int32_t>& packed, std::string& err) {
+  const int nit = (int)item_tab.size() / 8;
+  for (int ii = 0; ii < nit; ii++) {
+    const int32_t* I = &item_tab[8 * (size_t)ii];
+    if (I[0] >= 65536 || (I[1] != 3 && (I[5] >= 65536 || I[6] + 1 >= 65536))) return refuse(err, MM_EUNSUPPORTED, "tendon path beyond the engine's table limits");
+    packed.push_back(I[0] | (I[1] << 16));
+    packed.push_back(I[1] == 3 ? I[3] : (I[3] | (I[4] << 16)));
+    packed.push_back(I[1] == 3 ? I[4] : (I[5] | ((I[6] + 1) << 16)));
+    packed.push_back(I[7]);
+  }
+  return MM_OK;
+}
+
+// the tendons' constant length (path segments folded at create): [ntendon] float for the fp32 kernels (padded to an even count),
+// then [ntendon] double for the precision-mode kernels
+static inline std::vector<int32_t> ten_len0_words(const Dims& d, const std::vector<double>& ten_len0, int& f64_at) {
+  std::vector<int32_t> l0;
+  const int nt_ = std::max(d.ntendon, 1), ntp = (nt_ + 1) & ~1;
+  for (int t = 0; t < ntp; t++) { const float f = t < d.ntendon ? (float)ten_len0[t] : 0.f; int32_t w; memcpy(&w, &f, 4); l0.push_back(w); }
+  for (int t = 0; t < nt_; t++) { const double v = t < d.ntendon ? ten_len0[t] : 0.0; int32_t w[2]; memcpy(w, &v, 8); l0.push_back(w[0]); l0.push_back(w[1]); }
+  f64_at = ntp;
+  return l0;
+}
+
+// per dof: 64-bit mask of the dofs on its kinematic chain; per body: of the dofs between the body and the root of its tree
+static inline void dof_masks(const BlobView& b, const Dims& d, std::vector<int32_t>& rel, std::vector<int32_t>& bm) {
+  const int32_t *dpar = b.i(MM_SEC_DOF_PARENTID), *bpar = b.i(MM_SEC_BODY_PARENT), *bdofadr = b.i(MM_SEC_BODY_DOFADR);
+  const int32_t *bdofnum = b.i(MM_SEC_BODY_DOFNUM);
+  rel.assign(2 * (size_t)d.nv, 0);
+  for (int i = 0; i < d.nv && d.nv <= 64; i++)
+    for (int k = i; k >= 0; k = dpar[k]) {   // k is an ancestor-or-self of i: the pair is on one chain, both ways
+      rel[2 * i + (k >> 5)] |= (int32_t)(1u << (k & 31));
+      rel[2 * k + (i >> 5)] |= (int32_t)(1u << (i & 31));
+    }
+  bm.assign(2 * (size_t)d.nbody, 0);
+  for (int k = 1; k < d.nbody && d.nv <= 64; k++) {
+    if (bpar[k] > 0) { bm[2 * k] = bm[2 * bpar[k]]; bm[2 * k + 1] = bm[2 * bpar[k] + 1]; }     // parent < child: already final
+    for (int i = bdofadr[k]; i >= 0 && i < bdofadr[k] + bdofnum[k]; i++) bm[2 * k + (i >> 5)] |= (int32_t)(1u << (i & 31));
+  }
+}
+
+// one word pair per joint for the per-body joint loops (Engine::kinematics / velocity_bias): type | dofadr << 4 | qposadr << 14,
+// bits(qpos0[qposadr])
+static inline int joint_words(const BlobView& b, const Dims& d, std::vector<int32_t>& jp, std::string& err) {
+  const int32_t *jt = b.i(MM_SEC_JNT_TYPE), *jd = b.i(MM_SEC_JNT_DOFADR), *jq = b.i(MM_SEC_JNT_QPOSADR);
+  const uint32_t *q0 = b.u(MM_SEC_QPOS0);
+  jp.assign(2 * (size_t)std::max(d.njnt, 1), 0);
+  for (int j = 0; j < d.njnt; j++) {
+    if (jd[j] < 0 || jd[j] >= 1024 || jq[j] < 0 || jq[j] >= 1024) return refuse(err, MM_EUNSUPPORTED, "joint addresses beyond the engine's packed joint word (1024 dofs / qpos words)");
+    jp[2 * j] = (int32_t)(jt[j] | (jd[j] << 4) | (jq[j] << 14));
+    jp[2 * j + 1] = (int32_t)q0[jq[j]];
+  }
+  return MM_OK;
+}
+
+// chains of the body tree (Engine::subtree_sum).  A body starts a chain when it hangs off the world or its parent has
+// another child too; the bodies of a chain must have consecutive ids (MuJoCo's depth-first numbering gives that).
+// Sets Dims::bchain_nlevel (0: the chains could not be built).
+static inline std::vector<int32_t> body_chains(const BlobView& b, Dims& d) {
+  const int32_t *bpar = b.i(MM_SEC_BODY_PARENT);
+  std::vector<int32_t> tab(3 * (size_t)std::max(d.nbody, 1), -1);
+  std::vector<int> nchb(d.nbody, 0), top_of(d.nbody, 0), lvl(d.nbody, 0);
+  for (int k = 1; k < d.nbody; k++) if (bpar[k] > 0) nchb[bpar[k]]++;
+  bool ok = d.nbody <= 255;
+  int nlev = 0;
+  for (int k = 1; k < d.nbody && ok; k++) {
+    const int p = bpar[k];
+    if (p > 0 && nchb[p] == 1) {             // continues its parent's chain
+      if (p != k - 1) { ok = false; break; }
+      top_of[k] = top_of[p];
+      tab[3 * (size_t)top_of[k]] = (tab[3 * (size_t)top_of[k]] & ~255) | k;   // new bottom
+      continue;
+    }
+    top_of[k] = k;
+    lvl[k] = p > 0 ? lvl[top_of[p]] + 1 : 0;
+    if (lvl[k] > 15) { ok = false; break; }
+    nlev = std::max(nlev, lvl[k] + 1);
+    tab[3 * (size_t)k] = k | (lvl[k] << 8);
+    tab[3 * (size_t)k + 1] = 0; tab[3 * (size_t)k + 2] = 0;
+    if (p > 0) {                             // register with the chain it hangs off (whose bottom is p)
+      int32_t* pt = &tab[3 * (size_t)top_of[p]];
+      const int c = (pt[0] >> 12) & 15;
+      if (c >= 8) { ok = false; break; }
+      pt[1 + (c >> 2)] |= (int32_t)((uint32_t)k << (8 * (c & 3)));
+      pt[0] = (pt[0] & ~(15 << 12)) | ((c + 1) << 12);
+    }
+  }
+  int maxch = 0, maxlen = 1;
+  for (int k = 1; k < d.nbody && ok; k++)
+    if (tab[3 * (size_t)k] >= 0) { maxch = std::max(maxch, (tab[3 * (size_t)k] >> 12) & 15); maxlen = std::max(maxlen, (tab[3 * (size_t)k] & 255) - k + 1); }
+  d.bchain_nlevel = ok ? (nlev | (maxch << 4) | (maxlen << 8)) : 0;
+  return tab;
+}
+
+// rows per lane and the default group width: the smallest that can own every body / dof / constraint row and has a compiled kernel
+static inline int choose_width(ModelImage& m, std::string& err) {
+  const Dims& d = m.d;
+  m.lanes = 0;
+  const int rk4 = integ_kernel(d.integrator);
+  // more rows than a wavefront has lanes: two rows per lane, up to MM_MAX_EFC_ROWS (njmax <= 64 routes exactly as before)
+  if (d.gen && d.njmax > MM_MAX_EFC_ROWS)
+    return refuse(err, MM_EUNSUPPORTED, "no compiled kernel owns this model (njmax > 128 constraint rows: the general-row kernels hold at most 128 rows per env, two per lane of a wavefront)");
+  m.rpl = (d.gen && d.njmax > 64) ? 2 : 1;
+  for (int c : {4, 8, 16, 32, 64}) if (check_lanes(&m, c) && have_kernel(c, m.nvp, d.gen, rk4, m.rpl)) { m.lanes = c; break; }
+  if (!m.lanes) {
+    // a model whose rows need a wider group than its dofs do (torso: 18 dofs, 33 rows): take the next larger dense tile
+    // that has a kernel at that width (the padding dofs are inert)
+    const int nvp_min = m.nvp;
+    for (int c : {4, 8, 16, 32, 64}) {
+      for (int n : kNvpChoices) {
+        if (n <= nvp_min) continue;
+        m.nvp = n;
+        if (check_lanes(&m, c) && have_kernel(c, n, d.gen, rk4, m.rpl)) { m.lanes = c; break; }
+      }
+      if (m.lanes) break;
+    }
+    if (!m.lanes) m.nvp = nvp_min;
+  }
+  if (!m.lanes && m.rpl == 2) return refuse(err, MM_EUNSUPPORTED, "no compiled kernel owns this model (64 < njmax <= 128 takes the two-rows-per-lane kernels: Euler, nv <= 36, nbody / njnt / neq <= 64)");
+  if (!m.lanes) return refuse(err, MM_EUNSUPPORTED, "no compiled kernel owns this model (needs > 64 lanes per env: nbody, nv, njnt or constraint rows > 64)");
+  if (d.gen || rk4) m.lanes_auto = 0;   // row tables are sized for one group width; RK4 kernels exist for the default width only
+  return MM_OK;
+}
+
+}   // namespace mmc
+
+// model blob -> ModelImage; an MM_* code, with the reason in `err` when it is not MM_OK
+static inline int compile_model(const uint32_t* blob, int nwords, ModelImage& m, std::string& err) {
+  using namespace mmc;
+  BlobView b;
+  if (int rc = open_blob(blob, nwords, b, err)) return rc;
+  memcpy(m.sec, b.sec, sizeof(m.sec));
+  Dims& d = m.d;
+  if (int rc = read_dims(b, d, err)) return rc;
+  const DofTree tree = build_dof_tree(b, d);
+  m.nseg = tree.nseg;
+  if (int rc = check_rows(b, d, m.nvp, err)) return rc;
+
+  // ---- engine-private tables
+  const BodyTables bt = body_tables(b, d);
+  const RefFrames ref = reference_frames(b, d);
+  const std::vector<int32_t> item_tab = tendon_path_items(b, d, ref, m);
+  std::vector<int32_t> jent, jrow, packed, rel, bm, jp;
+  if (int rc = tendon_jacobian_rows(b, d, item_tab, jent, jrow, err)) return rc;
+  reference_origin(ref, d, m.origin);
+  d.ox = m.origin[0]; d.oy = m.origin[1]; d.oz = m.origin[2];
+
+  std::vector<uint32_t>& dev = m.words;
+  dev.assign(blob, blob + nwords);
+  auto append = [&](const std::vector<int32_t>& v, size_t align = 1) {
+    while (dev.size() % align) dev.push_back(0u);
+    int off = (int)dev.size();
+    for (int32_t x : v) dev.push_back((uint32_t)x);
+    if (v.empty()) dev.push_back(0);
+    return off;
+  };
+  m.x.body_depth = append(bt.depth); m.x.body_rootslot = append(bt.rootslot); m.x.dof_rootslot = append(bt.dofslot);
+  m.x.root_list = append(bt.roots); m.x.nroot = (int)bt.roots.size();
+  m.x.jent = append(jent);
+  m.x.jrec = append(jrow, 4);   // 16-byte rows
+  if (int rc = pack_path_items(item_tab, packed, err)) return rc;
+  m.x.item_tab = append(packed, 4); m.x.nitem = (int)item_tab.size() / 8;
+  int f64_at = 0;
+  m.x.ten_len0 = append(ten_len0_words(d, m.ten_len0, f64_at), 2);   // the double table is 8-byte aligned
+  m.x.ten_len0_f64 = m.x.ten_len0 + f64_at;
+  dof_masks(b, d, rel, bm);
+  m.x.dof_rel = append(rel);
+  m.x.body_dofmask = append(bm);
+  m.x.dof_desc = append(tree.desc); m.x.dof_seg = append(tree.seg); m.x.dof_anc = append(tree.anc);
+  if (int rc = joint_words(b, d, jp, err)) return rc;
+  m.x.jnt_pack = append(jp);
+  m.x.body_chain = append(body_chains(b, d));
+  m.blob_words = (int)dev.size();
+  m.cofs = (int)dev.size();          // ConstBlock (dims / LDS layout / aux offsets): global-only tail, not staged into LDS
+  m.cofs_tw = m.cofs + kConstWords;  // the same for two-wave launches (their LDS layout differs)
+  dev.resize(dev.size() + 2 * (size_t)kConstWords, 0u);
+
+  if (int rc = choose_width(m, err)) return rc;
+  build_layout(&m);
+  write_consts(&m);
+  return MM_OK;
+}

@@ -257,6 +257,7 @@ def lib():
         L.mm_last_error.restype = C.c_char_p
         L.mm_version.restype = C.c_char_p
         L.mm_debug_layout.argtypes = [C.c_void_p, C.c_char_p]
+        L.mm_debug_model_image.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.mm_debug_set_dump.argtypes = [C.c_void_p]
         L.mm_debug_set_prof.argtypes = [C.c_void_p]
         L.mm_model_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
@@ -357,6 +358,18 @@ class HipModel:
 
     def layout(self, name: str) -> int:
         return lib().mm_debug_layout(self.h, name.encode())
+
+    def set_lanes(self, lanes_per_env: int):
+        _chk(lib().mm_model_set_lanes(self.h, int(lanes_per_env)), "mm_model_set_lanes")
+
+    def debug_image(self) -> np.ndarray:
+        """the device image read back (mm_debug_model_image): model words [0, MM_INFO_MODEL_WORDS), then the two constant blocks"""
+        cap = self.info(INFO_MODEL_WORDS) + 1024
+        out = np.zeros(cap, dtype=np.uint32)
+        with torch.cuda.device(self.device):
+            n = lib().mm_debug_model_image(self.h, out.ctypes.data, cap)
+        _chk(min(n, 0), "mm_debug_model_image")
+        return out[:n].copy()
 
     def __del__(self):
         try:
