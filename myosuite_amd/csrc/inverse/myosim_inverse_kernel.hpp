@@ -1,0 +1,212 @@
+#pragma once
+// myosim_inverse_kernel.hpp -- batched inverse dynamics (mj_inverse) for gfx950: k_inverse<G, NVP, GEN>.
+//
+// The engine's forward stages composed in the inverse order.  Same execution model as k_engine (myosim_engine_common.hpp): a group of
+// G lanes owns one env, lane g is body g / dof g / constraint row g; one wave per env group, no helper waves (KArgs::two_wave = 0,
+// the one-wave LDS layout), the model read through L2.  Per env:
+//
+//   kinematics -> comPos -> tendon -> [constraint rows] -> comVel / RNE bias (+ tendon velocities) -> CRB
+//   qfrc_mass       = M qacc                       (mul_m: dense rows, or the tree-sparse rows of the SP family; nothing is factorised)
+//   qfrc_passive    = joint springs + dampers, tendon springs + dampers through J'      (no actuator term)
+//   qfrc_constraint = J' f(J qacc - aref)          (mj_invConstraint: the row law of the forward solve, evaluated once)
+//   qfrc_inverse    = qfrc_mass + qfrc_bias - qfrc_passive - qfrc_constraint
+//
+// The engine headers are included read-only; what Engine lacks lives in InvEngine below.  The kernels are linked into a library of
+// their own (libmyosim_inverse.so): the engine library's kernel set is pinned by tests/test_rows128.py.
+#include "../myosim_engine_kernel.hpp"
+#include "../myosim_inst_list.hpp"
+
+// per-call arguments behind KArgs (KA() reads the kernarg segment as KArgs: that struct stays the first parameter)
+struct InvArgs {
+  const float* qacc;        // [nenv][nv]
+  int constraints;          // 0: mjDSBL_CONSTRAINT; 1: mj_invConstraint
+  float* qfrc_inverse;      // [nenv][nv]
+  float *qfrc_mass, *qfrc_bias, *qfrc_passive, *qfrc_constraint;   // [nenv][nv] or null
+  int32_t* nefc;            // [nenv] or null
+  float* actuator_moment;   // [nenv][nu][nv] or null
+  float *actuator_gain, *actuator_bias, *actuator_length, *actuator_velocity;   // [nenv][nu] or null
+};
+
+template <int G, int NVP, bool GEN>
+struct InvEngine : Engine<G, NVP, GEN, 0> {
+  using Base = Engine<G, NVP, GEN, 0>;
+  __device__ __forceinline__ InvEngine(const KArgs& a_, const uint32_t* mb_, real* W_, int g_) : Base(a_, mb_, W_, g_) {}
+
+  // qfrc_passive of dof g: Engine::actuation() without its actuator loop (tendon springs / dampers, J' f) plus the joint terms of
+  // Engine::smooth_force().  Needs the tendon lengths, the tendon velocities (velocity_bias) and the tendon Jacobian.
+  __device__ __forceinline__ real passive_force() {
+    const KArgs& a = this->a;
+    const uint32_t* mb = this->mb;
+    real* W = this->W;
+    const int g = this->g;
+    const auto& L = KL();
+    for (int t = g; t < KD().ntendon; t += G) {
+      real k = MF_(TENDON_STIFFNESS)[t], bd = MF_(TENDON_DAMPING)[t], f = 0.f;
+      if (k != 0.f || bd != 0.f) {
+        real len = W[L.tenlen + t], lo = MF_(TENDON_LENGTHSPRING)[2 * t], hi = MF_(TENDON_LENGTHSPRING)[2 * t + 1];
+        if (len > hi) f = k * (hi - len);
+        else if (len < lo) f = k * (lo - len);
+        f -= bd * W[L.tenvel + t];
+      }
+      W[L.tenfrc + t] = f;
+    }
+    if (g < KD().nv) W[L.vec + g] = 0.f;
+    GSYNC();
+    {
+      int s_ja = SECOFF_(TENJ_ADR), s_jd = SECOFF_(TENJ_DOF), o_tj = L.tenj, o_vec = L.vec, o_tf = L.tenfrc;
+      PIN_S(s_ja); PIN_S(s_jd); PIN_S(o_tj); PIN_S(o_vec); PIN_S(o_tf);
+      for (int t = g; t < KD().ntendon; t += G) {
+        real f = W[o_tf + t];
+        const int e0 = AI_(s_ja)[t], e1 = AI_(s_ja)[t + 1];
+        if (f != 0.f)
+          for (int e = e0; e < e1; e++) atomicAdd(&W[o_vec + AI_(s_jd)[e]], W[o_tj + e] * f);
+      }
+    }
+    GSYNC();
+    real s = 0.f;
+    if (g < KD().nv) {
+      s = -MF_(DOF_DAMPING)[g] * this->d_qvel + W[L.vec + g];
+      const int j = this->c_rowj;                       // = DOF_JNTID[g]
+      const real ks = MF_(JNT_STIFFNESS)[j];
+      const int type = MI_(JNT_TYPE)[j], qa = MI_(JNT_QPOSADR)[j];
+      const real qs = W[L.qpos + qa], q0s = MF_(QPOS_SPRING)[qa];
+      if (ks != 0.f && (type == MM_JNT_HINGE || type == MM_JNT_SLIDE)) s -= ks * (qs - q0s);
+    }
+    return s;
+  }
+
+  // qfrc_constraint of dof g at the given acceleration (mj_invConstraint).  The row scalars D, aref and the friction-loss bound are
+  // final when make_constraint() returns (limit rows: in make_constraint; general rows: in the owner stage of make_constraint_gen);
+  // the forward solve only iterates on qacc.  So this is one evaluation of the row law: jar = J qacc - aref, the row force, J' f.
+  // (Written out rather than a zero-iteration solve_constraints(): that one may start from qacc_smooth instead of the given qacc.)
+  __device__ __forceinline__ real constraint_force(real qacc) {
+    if constexpr (GEN) {
+      if (this->nrows_wave == 0) return 0.f;              // wave-uniform
+      this->r_jar = this->jac_mul(qacc) - this->r_aref;
+      bool quad;
+      const real f = this->row_force(this->r_jar, quad);
+      return this->jacT_mul(f);
+    } else {
+      // one potential limit row per joint, owned by lane j; J is a signed unit row on the joint's dof
+      this->r_jar = this->r_sign * sh<G>(qacc, this->r_dof) - this->r_aref;
+      const bool on = this->r_active && this->r_jar < 0.f;
+      const real f = on ? -this->r_D * this->r_jar : 0.f;
+      return this->rows_to_dof(this->r_sign * f);
+    }
+  }
+
+  // per-actuator outputs: length, velocity, gain(l, v), bias(l, v) -- force = gain * act + bias, as Engine::actuation() -- and the
+  // dense moment row (gear * tendon Jacobian row | gear at the joint's dof)
+  __device__ __forceinline__ void actuator_outputs(const InvArgs& v, int e, bool dup) {
+    const KArgs& a = this->a;
+    const uint32_t* mb = this->mb;
+    real* W = this->W;
+    const int g = this->g;
+    const auto& L = KL();
+    const int nu = KD().nu, nv = KD().nv;
+    for (int u = g; u < nu; u += G) {
+      const int id = MI_(ACT_TRNID)[u], f_tt = MI_(ACT_TRNTYPE)[u], f_gt = MI_(ACT_GAINTYPE)[u], f_bt = MI_(ACT_BIASTYPE)[u];
+      const real gear = MF_(ACT_GEAR)[u];
+      const real lr0 = MF_(ACT_LENGTHRANGE)[2 * u], lr1 = MF_(ACT_LENGTHRANGE)[2 * u + 1], acc0 = MF_(ACT_ACC0)[u];
+      real gp[9], bp[9];
+#pragma unroll
+      for (int k = 0; k < 9; k++) { gp[k] = MF_(ACT_GAINPRM)[9 * u + k]; bp[k] = MF_(ACT_BIASPRM)[9 * u + k]; }
+      const bool ten = f_tt == MM_TRN_TENDON;
+      const int dofadr = ten ? 0 : MI_(JNT_DOFADR)[id];
+      real len, vel;
+      if (ten) { len = gear * W[L.tenlen + id]; vel = gear * W[L.tenvel + id]; }
+      else { len = gear * W[L.qpos + MI_(JNT_QPOSADR)[id]]; vel = gear * W[L.qvel + dofadr]; }
+      real gain, bias = 0.f;
+      if (f_gt == MM_GAIN_MUSCLE) gain = muscle_gain(len, vel, lr0, lr1, acc0, gp);
+      else gain = gp[0];
+      if (f_bt == MM_BIAS_MUSCLE) bias = muscle_bias(len, lr0, lr1, acc0, bp);
+      else if (f_bt == MM_BIAS_AFFINE) bias = bp[0] + bp[1] * len + bp[2] * vel;
+      if (dup) continue;
+      const size_t k = (size_t)e * nu + u;
+      if (v.actuator_length) v.actuator_length[k] = len;
+      if (v.actuator_velocity) v.actuator_velocity[k] = vel;
+      if (v.actuator_gain) v.actuator_gain[k] = gain;
+      if (v.actuator_bias) v.actuator_bias[k] = bias;
+      if (v.actuator_moment) {
+        float* row = v.actuator_moment + k * (size_t)nv;      // this lane owns the whole row
+        for (int i = 0; i < nv; i++) row[i] = 0.f;
+        if (ten) {
+          const int e0 = MI_(TENJ_ADR)[id], e1 = MI_(TENJ_ADR)[id + 1];
+          for (int q = e0; q < e1; q++) row[MI_(TENJ_DOF)[q]] += gear * W[L.tenj + q];
+        } else row[dofadr] = gear;
+      }
+    }
+  }
+};
+
+template <int G, int NVP, bool GEN>
+__global__ void __launch_bounds__(512) k_inverse(KArgs a, InvArgs v) {
+  extern __shared__ real lds[];
+  constexpr int EPW = 64 / G;  // envs per wave
+  const int lane = threadIdx.x & 63;
+  const int wpb = blockDim.x >> 6;
+  const int wave = (int)(threadIdx.x >> 6);
+  const int g = lane % G;
+  const uint32_t* mb = a.blob;   // model through L2
+  int e = (blockIdx.x * wpb + wave) * EPW + lane / G;
+  const int nenv = a.s.nenv;
+  if ((blockIdx.x * wpb + wave) * EPW >= nenv) return;  // whole wave idle
+  const bool dup = e >= nenv;
+  if (dup) e = nenv - 1;  // surplus groups recompute the last env (they never store)
+  real* W = lds + (size_t)(wave * EPW + lane / G) * KL().total;
+  const auto& L = KL();
+  const auto& d = KD();
+  InvEngine<G, NVP, GEN> E(a, mb, W, g);
+  E.env = e;
+
+  // ---- load state and the acceleration (the state rows are read-only here)
+  for (int i = g; i < d.nq; i += G) W[L.qpos + i] = a.s.qpos[(size_t)e * d.nq + i];
+  real qacc = 0.f;
+  if (g < d.nv) {
+    E.d_qvel = a.s.qvel[(size_t)e * d.nv + g];
+    W[L.qvel + g] = E.d_qvel;
+    qacc = v.qacc[(size_t)e * d.nv + g];
+  }
+  GSYNC();
+
+  // ---- position and velocity stages, in the order of Engine::forward()
+  MM_FENCE(); E.kinematics();
+  MM_FENCE(); E.com_pos();
+  MM_FENCE(); E.tendon();
+  MM_FENCE();
+  if (v.constraints) E.make_constraint();
+  MM_FENCE(); E.velocity_bias();       // d_bias; tendon velocities
+  MM_FENCE(); E.crb();
+  MM_FENCE();
+
+  // ---- the four terms
+  const real f_mass = E.mul_m(qacc);
+  MM_FENCE();
+  const real f_pass = E.passive_force();
+  MM_FENCE();
+  real f_con = 0.f;
+  if (v.constraints) f_con = E.constraint_force(qacc);
+  MM_FENCE();
+  if (v.actuator_moment || v.actuator_gain || v.actuator_bias || v.actuator_length || v.actuator_velocity) E.actuator_outputs(v, e, dup);
+
+  if (dup) return;
+  if (g < d.nv) {
+    const size_t k = (size_t)e * d.nv + g;
+    v.qfrc_inverse[k] = f_mass + E.d_bias - f_pass - f_con;
+    if (v.qfrc_mass) v.qfrc_mass[k] = f_mass;
+    if (v.qfrc_bias) v.qfrc_bias[k] = E.d_bias;
+    if (v.qfrc_passive) v.qfrc_passive[k] = f_pass;
+    if (v.qfrc_constraint) v.qfrc_constraint[k] = f_con;
+  }
+  if (g == 0 && v.nefc) v.nefc[e] = v.constraints ? E.nefc : 0;
+}
+
+// the Euler entries of the engine's kernel list: X(lanes, padded nv, general rows, integrator) -> one k_inverse per (lanes, nvp, gen)
+#define MMI_INST_0(G_, N_, GN_) template __global__ void k_inverse<G_, N_, GN_ != 0>(KArgs, InvArgs);
+#define MMI_INST_1(G_, N_, GN_)
+#define MMI_INST_2(G_, N_, GN_)
+#define MMI_INSTANTIATE(G_, N_, GN_, RK_) MMI_INST_##RK_(G_, N_, GN_)
+#define MMI_DECL_0(G_, N_, GN_) extern template __global__ void k_inverse<G_, N_, GN_ != 0>(KArgs, InvArgs);
+#define MMI_DECL_1(G_, N_, GN_)
+#define MMI_DECL_2(G_, N_, GN_)
+#define MMI_DECLARE(G_, N_, GN_, RK_) MMI_DECL_##RK_(G_, N_, GN_)

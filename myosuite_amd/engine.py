@@ -95,8 +95,18 @@ FILE_FLAGS = {"myosim_inst_B.hip": ["-mllvm", "-sink-insts-to-avoid-spills=1", "
 
 
 def build(force: bool = False, verbose: bool = False, jobs: int = 0) -> str:
-    """Compile the HIP engine for gfx950 in-tree (hipcc cross-compiles without a GPU).  The kernel instantiations are
-    spread over several translation units (myosim_inst_*.hip) that are compiled in parallel and linked into one .so."""
+    """Compile the native libraries for gfx950 in-tree (hipcc cross-compiles without a GPU): the engine, libmyosim_hip.so, from
+    the *.hip files directly under csrc/, then the inverse-dynamics library, libmyosim_inverse.so, from csrc/inverse/
+    (myosuite_amd/inverse.py).  Returns the engine library's path."""
+    path = _build_engine(force=force, verbose=verbose, jobs=jobs)
+    from . import inverse
+    inverse.build(force=force, verbose=verbose, jobs=jobs)
+    return path
+
+
+def _build_engine(force: bool = False, verbose: bool = False, jobs: int = 0) -> str:
+    """The engine library.  The kernel instantiations are spread over several translation units (myosim_inst_*.hip) that are
+    compiled in parallel and linked into one .so."""
     import concurrent.futures
     srcs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip"))
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hpp", ".inc"))] + \

@@ -1,0 +1,211 @@
+"""Batched inverse dynamics (MuJoCo's mj_inverse) on the GPU: ctypes binding of libmyosim_inverse.so (include/myosim_inverse.h).
+
+    qfrc_inverse = M qacc + qfrc_bias - qfrc_passive - qfrc_constraint
+
+for every env of a batch in one launch of the HIP kernel k_inverse (myosuite_amd/csrc/inverse/).  The frames of a trajectory are
+independent, so a trajectory is a batch: inverse_dynamics_trajectory() is the reference tutorial's `get_qfrc`
+(tutorials/6_Inverse_Dynamics.ipynb) over all frames at once.  The optional actuator outputs (moment, gain, bias) are the inputs of
+that tutorial's QP for the muscle controls; the QP itself is not part of this package.
+
+The library is separate from libmyosim_hip.so (its kernel set is pinned by a test) and has a model handle of its own.  There is no
+CPU fallback: a missing library or a refused call raises.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import subprocess
+from typing import Dict, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import engine as E
+
+CSRC = os.path.join(E.CSRC, "inverse")
+LIB_PATH = os.path.join(E.CSRC, "libmyosim_inverse.so")
+MM_INVERSE_ABI_VERSION = 1   # include/myosim_inverse.h
+(INFO_LANES, INFO_KERNEL_FAMILY, INFO_EFC_ROWS, INFO_NVP, INFO_NV, INFO_NU, INFO_NQ, INFO_LDS_PER_ENV, INFO_ARGS_SIZE) = range(9)
+MAX_BUILD_JOBS = 16
+# the general-row units take the flag the engine's general-row units take (engine.FILE_FLAGS)
+FILE_FLAGS = {"myosim_inverse_inst_D.hip": ["-mllvm", "-sink-insts-to-avoid-spills=1"],
+              "myosim_inverse_inst_H.hip": ["-mllvm", "-sink-insts-to-avoid-spills=1"]}
+_lib = None
+
+_NV_OUT = ("qfrc_mass", "qfrc_bias", "qfrc_passive", "qfrc_constraint")
+_NU_OUT = ("actuator_gain", "actuator_bias", "actuator_length", "actuator_velocity")
+OUTPUTS = ("qfrc_inverse",) + _NV_OUT + ("nefc", "actuator_moment") + _NU_OUT
+
+
+class mm_inverse_args(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("constraints", C.c_int), ("qfrc_inverse", C.c_void_p),
+                ("qfrc_mass", C.c_void_p), ("qfrc_bias", C.c_void_p), ("qfrc_passive", C.c_void_p), ("qfrc_constraint", C.c_void_p),
+                ("nefc", C.c_void_p), ("actuator_moment", C.c_void_p),
+                ("actuator_gain", C.c_void_p), ("actuator_bias", C.c_void_p), ("actuator_length", C.c_void_p),
+                ("actuator_velocity", C.c_void_p)]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.size = C.sizeof(mm_inverse_args)
+
+
+def build(force: bool = False, verbose: bool = False, jobs: int = 0) -> str:
+    """Compile libmyosim_inverse.so for gfx950 in-tree (engine.build() calls this: one build step for both libraries).  Same
+    flags, flag stamp and mtime rule as the engine library; objects under csrc/_build/inverse/."""
+    import concurrent.futures
+    srcs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip"))
+    hdrs = [os.path.join(d, f) for d in (CSRC, E.CSRC) for f in os.listdir(d) if f.endswith((".hpp", ".inc"))] + \
+           [os.path.join(E._HERE, "..", "include", h) for h in ("myosim.h", "myosim_model.h", "myosim_inverse.h")]
+    bdir = os.path.join(E.CSRC, "_build", "inverse")
+    stamp, flags_now = os.path.join(bdir, "flags.txt"), " ".join(E.EXTRA_FLAGS) + " | " + repr(sorted(FILE_FLAGS.items()))
+    same_flags = os.path.exists(stamp) and open(stamp).read() == flags_now
+    force = force or (os.path.exists(LIB_PATH) and os.path.isdir(bdir) and not same_flags)
+    if not force and os.path.exists(LIB_PATH) and (same_flags or not os.path.isdir(bdir)) and \
+            all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in srcs + hdrs):
+        return LIB_PATH
+    os.makedirs(bdir, exist_ok=True)
+    newest_hdr = max(os.path.getmtime(h) for h in hdrs)
+
+    def compile_one(src):
+        obj = os.path.join(bdir, os.path.basename(src)[:-4] + ".o")
+        if not force and os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(src), newest_hdr):
+            return obj
+        cmd = (["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"] + E.EXTRA_FLAGS + FILE_FLAGS.get(os.path.basename(src), []) +
+               ["-mllvm", f"-amdgpu-sched-strategy={E.SCHED_STRATEGY['default']}", "-c", "-o", obj, src])
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+        return obj
+    workers = min(jobs or (os.cpu_count() or 1), len(srcs), MAX_BUILD_JOBS)
+    with concurrent.futures.ThreadPoolExecutor(max_workers=max(workers, 1)) as ex:
+        objs = list(ex.map(compile_one, srcs))
+    cmd = ["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_PATH] + objs
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    with open(stamp, "w") as f:
+        f.write(flags_now)
+    return LIB_PATH
+
+
+def lib():
+    """Load libmyosim_inverse.so; raises (never falls back) when it is absent."""
+    global _lib
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            raise E.EngineError(f"{LIB_PATH} not found: the inverse-dynamics library is not built. Run `python -c 'import "
+                                f"__graft_entry__ as g; g.build()'` (needs hipcc). There is no CPU fallback.")
+        L = C.CDLL(LIB_PATH)
+        L.mm_inverse_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        L.mm_inverse_destroy.argtypes = [C.c_void_p]
+        L.mm_inverse_destroy.restype = None
+        L.mm_inverse_last_error.restype = C.c_char_p
+        L.mm_inverse_info.argtypes = [C.c_void_p, C.c_int]
+        L.mm_inverse.argtypes = [C.c_void_p, C.POINTER(E.mm_state), C.c_void_p, C.POINTER(mm_inverse_args), C.c_void_p]
+        if L.mm_inverse_abi_version() != MM_INVERSE_ABI_VERSION:
+            raise E.EngineError(f"{LIB_PATH} speaks ABI {L.mm_inverse_abi_version()}, this binding {MM_INVERSE_ABI_VERSION}: rebuild the library")
+        _lib = L
+    return _lib
+
+
+def _chk(rc: int, what: str):
+    if rc != 0:
+        raise E.EngineError(f"{what} failed (rc={rc}): {lib().mm_inverse_last_error().decode()}")
+
+
+class InverseModel:
+    """Device-resident compiled model of the inverse library (mm_inverse_model)."""
+
+    def __init__(self, compiled, lanes_per_env: int = 0, device: Optional[torch.device] = None):
+        self.cm = compiled
+        if not torch.cuda.is_available():
+            raise E.EngineError("no HIP device visible: the inverse dynamics only run on the GPU (no CPU fallback)")
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        blob = np.ascontiguousarray(compiled.blob, dtype=np.uint32)
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            _chk(lib().mm_inverse_create(blob.ctypes.data, int(blob.size), int(lanes_per_env), C.byref(h)), "mm_inverse_create")
+        self.h = h
+        if lib().mm_inverse_info(h, INFO_ARGS_SIZE) != C.sizeof(mm_inverse_args):
+            raise E.EngineError("struct layout mismatch: mm_inverse_args (include/myosim_inverse.h changed without inverse.py)")
+
+    def info(self, which: int) -> int:
+        return lib().mm_inverse_info(self.h, which)
+
+    def __del__(self):
+        try:
+            h, self.h = getattr(self, "h", None), None
+            if h and _lib is not None:
+                _lib.mm_inverse_destroy(h)
+        except Exception:
+            pass
+
+
+def _state_struct(model: InverseModel, state):
+    """mm_state of a BatchState, or of a (qpos, qvel) pair of [n, nq] / [n, nv] float32 device tensors; returns (struct, nenv, keepalive)"""
+    if isinstance(state, E.BatchState):
+        if state.qpos.dtype != torch.float32:
+            raise E.EngineError("mm_inverse: fp64 state rows (MM_PREC_F64_STATE) are not offered")
+        return state._c, state.nenv, state
+    qpos, qvel = state
+    cm = model.cm
+    n = int(qpos.shape[0])
+    for t, w in ((qpos, cm.nq), (qvel, cm.nv)):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (n, w), (t.dtype, tuple(t.shape), (n, w))
+    return E.mm_state(n, qpos.data_ptr(), qvel.data_ptr(), None, None, None, None, None, -1, None, None, -1, None, -1, 0), n, (qpos, qvel)
+
+
+def inverse(model: InverseModel, state, qacc: torch.Tensor, constraints: bool = False,
+            want: Sequence[str] = ("qfrc_inverse",), out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+    """mm_inverse: one launch over the batch.  `state` is a BatchState or a (qpos [n, nq], qvel [n, nv]) pair; qacc is [n, nv].
+    Returns {name: tensor} for "qfrc_inverse" and every name in `want` (OUTPUTS); `out` supplies preallocated tensors."""
+    cm = model.cm
+    st, n, _keep = _state_struct(model, state)
+    assert qacc.is_cuda and qacc.dtype == torch.float32 and qacc.is_contiguous() and tuple(qacc.shape) == (n, cm.nv), (qacc.dtype, tuple(qacc.shape))
+    shapes = {"qfrc_inverse": (n, cm.nv), "nefc": (n,), "actuator_moment": (n, cm.nu, cm.nv)}
+    shapes.update({k: (n, cm.nv) for k in _NV_OUT})
+    shapes.update({k: (n, cm.nu) for k in _NU_OUT})
+    names = ["qfrc_inverse"] + [k for k in want if k != "qfrc_inverse"]
+    res: Dict[str, torch.Tensor] = {}
+    a = mm_inverse_args()
+    a.constraints = int(bool(constraints))
+    for k in names:
+        if k not in shapes:
+            raise ValueError(f"unknown inverse output {k!r}: one of {OUTPUTS}")
+        dt = torch.int32 if k == "nefc" else torch.float32
+        t = out[k] if out is not None and k in out else torch.zeros(shapes[k], dtype=dt, device=model.device)
+        assert t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shapes[k], (k, t.dtype, tuple(t.shape))
+        res[k] = t
+        setattr(a, k, t.data_ptr())
+    _chk(lib().mm_inverse(model.h, C.byref(st), qacc.data_ptr(), C.byref(a), E._stream(model.device)), "mm_inverse")
+    return res
+
+
+def trajectory_frames(qpos: torch.Tensor, h: float):
+    """The tutorial's per-frame finite differences for a trajectory qpos [T + 1, nq] (hinge / slide coordinates only: nq = nv):
+    frame t < T has  qvel_t = (q_t - q_{t-1}) / h  (zero at t = 0)  and  qacc_t = ((q_{t+1} - q_t) / h - qvel_t) / h.
+    Returns (qpos [T, nq], qvel [T, nv], qacc [T, nv])."""
+    q = qpos[:-1]
+    qvel = torch.zeros_like(q)
+    qvel[1:] = (qpos[1:-1] - qpos[:-2]) / h
+    qacc = ((qpos[1:] - q) / h - qvel) / h
+    return q.contiguous(), qvel.contiguous(), qacc.contiguous()
+
+
+def inverse_dynamics_trajectory(compiled, qpos, h: Optional[float] = None, constraints: bool = False,
+                                model: Optional[InverseModel] = None) -> torch.Tensor:
+    """qfrc_inverse [T, nv] of every frame of a joint-angle trajectory qpos [T + 1, nq] in ONE launch (the tutorial's get_qfrc; the
+    last point only closes the last frame's difference).  h defaults to the model's timestep.  Models with free or ball joints are
+    refused: differences of their coordinates need mj_differentiatePos."""
+    jt = np.asarray(compiled.arrays["JNT_TYPE"]).astype(np.int64)
+    from .model import spec as S
+    if compiled.nq != compiled.nv or np.any((jt == S.C["MM_JNT_FREE"]) | (jt == S.C["MM_JNT_BALL"])):
+        raise ValueError("inverse_dynamics_trajectory: the model has free or ball joints; finite differences of their coordinates "
+                         "need mj_differentiatePos (pass qvel / qacc to inverse() yourself)")
+    model = model if model is not None else InverseModel(compiled)
+    q = torch.as_tensor(qpos, dtype=torch.float32, device=model.device)
+    if q.dim() != 2 or q.shape[0] < 2 or q.shape[1] != compiled.nq:
+        raise ValueError(f"qpos must be [T + 1, nq = {compiled.nq}] with T >= 1, got {tuple(q.shape)}")
+    h = float(h if h is not None else compiled.timestep)
+    qp, qv, qa = trajectory_frames(q, h)
+    return inverse(model, (qp, qv), qa, constraints=constraints)["qfrc_inverse"]
