@@ -6,36 +6,27 @@
 #include <string>
 
 #include "myosim_inverse_kernel.hpp"
-#include "../myosim_model_compile.hpp"
+#include "../myosim_launch_plan.hpp"
 #include "../../../include/myosim_inverse.h"
 
 MM_KERNEL_LIST(MMI_DECLARE)
 
-struct mm_inverse_model : ModelImage {   // the compiled model (myosim_model_compile.hpp) + its device copy
-  uint32_t* d_blob = nullptr;
-  int device = 0;
-};
-
 static thread_local std::string g_err;
 static int fail(int code, const std::string& msg) { g_err = msg; return code; }
-#define HIPCHK(x)                                                                                 \
-  do {                                                                                            \
-    hipError_t e_ = (x);                                                                          \
-    if (e_ != hipSuccess) return fail(MM_EHIP, std::string(#x) + ": " + hipGetErrorString(e_));   \
-  } while (0)
+#define MM_HOST_FAIL fail
+#include "../myosim_host.hpp"
+
+struct mm_inverse_model : OnDevice<ModelImage> {};   // the compiled model (myosim_model_compile.hpp) + its device copy
 
 extern "C" const char* mm_inverse_last_error(void) { return g_err.c_str(); }
 extern "C" int mm_inverse_abi_version(void) { return MM_INVERSE_ABI_VERSION; }
 
-extern "C" void mm_inverse_destroy(mm_inverse_model* m) {
-  std::unique_ptr<mm_inverse_model> host(m);   // frees the host object on return
-  if (m && m->d_blob) (void)hipFree(m->d_blob);
-}
+extern "C" void mm_inverse_destroy(mm_inverse_model* m) { delete m; }
 
 extern "C" int mm_inverse_create(const uint32_t* blob, int nwords, int lanes_per_env, mm_inverse_model** out) {
   if (!out) return fail(MM_EARG, "mm_inverse_create: out is NULL");
   *out = nullptr;
-  std::unique_ptr<mm_inverse_model, void (*)(mm_inverse_model*)> m(new mm_inverse_model(), mm_inverse_destroy);
+  std::unique_ptr<mm_inverse_model> m(new mm_inverse_model());
   // The inverse has no integrator.  The model is compiled as an Euler model, so that the kernel family, the padded width and the
   // LDS layout are those of a (lanes, nvp, general rows) combination of the Euler list -- the combinations k_inverse is built for --
   // whatever integrator the blob names.
@@ -51,6 +42,7 @@ extern "C" int mm_inverse_create(const uint32_t* blob, int nwords, int lanes_per
     euler[b.sec[MM_SEC_OPT_I] + MM_OI_INTEGRATOR] = (uint32_t)MM_INT_EULER;
   }
   { const int rc = compile_model(euler.data(), nwords, *m, g_err); if (rc != MM_OK) return rc; }
+  m->lanes_auto = 0;   // one width per handle (the model's default, or lanes_per_env below), whatever the batch size
   if (m->rpl != 1)
     return fail(MM_EUNSUPPORTED, "mm_inverse: models with njmax > 64 (the two-rows-per-lane kernel family) have no inverse kernel");
   if (lanes_per_env) {
@@ -61,9 +53,7 @@ extern "C" int mm_inverse_create(const uint32_t* blob, int nwords, int lanes_per
     write_consts(m.get());
   }
   if (!have_kernel(m->lanes, m->nvp, m->d.gen, 0, 1)) return fail(MM_EUNSUPPORTED, "no compiled inverse kernel for this (lanes_per_env, nv) combination");
-  HIPCHK(hipGetDevice(&m->device));
-  HIPCHK(hipMalloc((void**)&m->d_blob, m->words.size() * sizeof(uint32_t)));
-  HIPCHK(hipMemcpy(m->d_blob, m->words.data(), m->words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  if (int rc = upload_model(m.get())) return rc;
   *out = m.release();
   return MM_OK;
 }
@@ -84,30 +74,14 @@ extern "C" int mm_inverse_info(const mm_inverse_model* m, int which) {
   return MM_EARG;
 }
 
-template <int G, int NVP, bool GEN>
-static int launch_k(const mm_inverse_model* m, const KArgs& a, const InvArgs& v, dim3 grid, dim3 block, size_t lds, hipStream_t st) {
-  // the dynamic-LDS limit is a per-device attribute of the function (set on every launch: the call is cheap next to the kernel)
-  HIPCHK(hipFuncSetAttribute((const void*)k_inverse<G, NVP, GEN>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  hipLaunchKernelGGL((k_inverse<G, NVP, GEN>), grid, block, lds, st, a, v);
-  HIPCHK(hipGetLastError());
-  (void)m;
-  return MM_OK;
-}
-
-static int launch_on_device(const mm_inverse_model* m, const KArgs& a, const InvArgs& v, void* stream) {
-  const int G = m->lanes, epw = 64 / G;
-  const size_t kLds = 160 * 1024;
-  const int waves_needed = (a.s.nenv + epw - 1) / epw;
-  int wpb = (waves_needed + 255) / 256;       // waves per CU that spread the batch over all 256 CUs in one round
-  if (wpb < 1) wpb = 1;
-  if (wpb > 8) wpb = 8;                        // __launch_bounds__(512)
-  while (wpb > 1 && (size_t)wpb * epw * m->lds_per_env > kLds) wpb--;
-  const int epb = epw * wpb;
-  const size_t lds = (size_t)epb * m->lds_per_env;
-  if (lds > kLds) return fail(MM_ELDS, "per-block LDS tables exceed 160 KiB");
-  dim3 grid((a.s.nenv + epb - 1) / epb), block(64 * wpb);
-  hipStream_t st = (hipStream_t)stream;
-#define X0(G_, N_, GN_) if (G == G_ && m->nvp == N_ && m->d.gen == GN_) return launch_k<G_, N_, GN_ != 0>(m, a, v, grid, block, lds, st);
+// the planner's geometry with the model read through L2 and no helper waves (k_inverse has neither form)
+static int launch_on_device(const mm_inverse_model* m, KArgs& a, const InvArgs& v, void* stream) {
+  LaunchOptions opt;
+  opt.lds_model = 0;
+  LaunchPlan p;
+  if (int rc = plan_launch(*m, opt, 0, a.s.nenv, false, p, g_err)) return rc;
+  const void* fn = nullptr;
+#define X0(G_, N_, GN_) if (p.lanes == G_ && m->nvp == N_ && m->d.gen == GN_) fn = (const void*)k_inverse<G_, N_, GN_ != 0>;
 #define X1(G_, N_, GN_)
 #define X2(G_, N_, GN_)
 #define X(G_, N_, GN_, RK_) X##RK_(G_, N_, GN_)
@@ -116,7 +90,13 @@ static int launch_on_device(const mm_inverse_model* m, const KArgs& a, const Inv
 #undef X0
 #undef X1
 #undef X2
-  return fail(MM_EUNSUPPORTED, "no compiled inverse kernel for this (lanes_per_env, nv) combination");
+  if (!fn) return fail(MM_EUNSUPPORTED, "no compiled inverse kernel for this (lanes_per_env, nv) combination");
+  // the dynamic-LDS limit is a per-device attribute of the function (set on every launch: the call is cheap next to the kernel)
+  HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  void* args[] = {&a, const_cast<InvArgs*>(&v)};
+  (void)hipLaunchKernel(fn, dim3(p.blocks), dim3(p.threads), args, p.lds_bytes, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return MM_OK;
 }
 
 extern "C" int mm_inverse(const mm_inverse_model* m, const mm_state* s, const float* qacc, const mm_inverse_args* args, void* stream) {
@@ -135,26 +115,15 @@ extern "C" int mm_inverse(const mm_inverse_model* m, const mm_state* s, const fl
   if (s->geom_size_env || s->geom_type_env || s->body_mass_env || s->body_pos_env)
     return fail(MM_EUNSUPPORTED, "mm_inverse: the state carries a per-env model delta (geom_size_env / geom_type_env / body_mass_env / body_pos_env), which the inverse does not implement");
   KArgs a;
-  memset(&a, 0, sizeof(a));
-  a.blob = m->d_blob; a.cofs = m->cofs;
-  memcpy(a.sec, m->sec, sizeof(a.sec));
-  a.d = m->d; a.L = m->L; a.D = m->D; a.x = m->x; a.s = *s;
-  a.s.geom_env_id = -1; a.s.body_mass_env_id = -1; a.s.body_pos_env_id = -1;
-  a.mode = 1; a.two_wave = 0; a.blob_words = m->blob_words;
+  fill_kargs(a, m, s);
+  a.mode = 1;
   InvArgs v;
   memset(&v, 0, sizeof(v));
   v.qacc = qacc; v.constraints = p.constraints ? 1 : 0;
   v.qfrc_inverse = p.qfrc_inverse; v.qfrc_mass = p.qfrc_mass; v.qfrc_bias = p.qfrc_bias; v.qfrc_passive = p.qfrc_passive;
   v.qfrc_constraint = p.qfrc_constraint; v.nefc = p.nefc; v.actuator_moment = p.actuator_moment; v.actuator_gain = p.actuator_gain;
   v.actuator_bias = p.actuator_bias; v.actuator_length = p.actuator_length; v.actuator_velocity = p.actuator_velocity;
-  // launch on the model's device (the caller's stream must belong to it); restore the caller's current device afterwards
-  int cur = -1;
-  HIPCHK(hipGetDevice(&cur));
-  if (cur != m->device) {
-    HIPCHK(hipSetDevice(m->device));
-    const int rc = launch_on_device(m, a, v, stream);
-    (void)hipSetDevice(cur);
-    return rc;
-  }
+  DeviceGuard guard(m->device);
+  if (guard.err != hipSuccess) return fail(MM_EHIP, guard.message());
   return launch_on_device(m, a, v, stream);
 }

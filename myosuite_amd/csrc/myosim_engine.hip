@@ -7,7 +7,7 @@
 #include <memory>
 #include "myosim_engine_kernel.hpp"
 #include "myosim_engine_kernel_f64.hpp"
-#include "myosim_model_compile.hpp"   // (includes myosim_inst_list.hpp)
+#include "myosim_launch_plan.hpp"   // (includes myosim_model_compile.hpp and myosim_inst_list.hpp)
 MM_KERNEL_LIST(MM_DECLARE)
 MM_KERNELS_OBS(MM_DECLARE_OBS)
 MM_KERNELS_S(MM_DECLARE_ROWS2)
@@ -175,22 +175,14 @@ __global__ void k_reset(ResetArgs r) {
 }
 
 // =========================================================================== host side
-struct mm_model : ModelImage {   // the compiled model (myosim_model_compile.hpp) + its device copy and launch options
-  uint32_t* d_blob = nullptr;
-  int lanes_user = 0;        // the width was pinned by the caller (mm_model_set_lanes), not chosen as the model's default
-  int waves_per_block = 0;   // 0 = auto
-  int lds_model = 1;
-  int device = 0;
-};
-
 static thread_local std::string g_err;
 static int g_two_wave = 1;   // MYOSIM_TWO_WAVE=0 switches the helper waves off (A/B, debugging)
 static int fail(int code, const std::string& msg) { g_err = msg; return code; }
-#define HIPCHK(x)                                                                                 \
-  do {                                                                                            \
-    hipError_t e_ = (x);                                                                          \
-    if (e_ != hipSuccess) return fail(MM_EHIP, std::string(#x) + ": " + hipGetErrorString(e_));   \
-  } while (0)
+#define MM_HOST_FAIL fail
+#include "myosim_host.hpp"
+
+// the compiled model (myosim_model_compile.hpp), its device copy and its launch options (myosim_launch_plan.hpp)
+struct mm_model : OnDevice<ModelImage>, LaunchOptions {};
 
 extern "C" const char* mm_last_error(void) { return g_err.c_str(); }
 extern "C" const char* mm_version(void) { return "myosim-hip 0.4 (gfx950, lane=item engine, ABI 7)"; }
@@ -211,72 +203,32 @@ static int upload_consts(mm_model* m) {
   return MM_OK;
 }
 
-extern "C" void mm_model_destroy(mm_model* m);
 extern "C" int mm_model_create(const uint32_t* blob, int nwords, mm_model** out) {
   { const char* tw = getenv("MYOSIM_TWO_WAVE"); if (tw) g_two_wave = atoi(tw) != 0; }
   if (!out) return fail(MM_EBADBLOB, "blob too short");
-  std::unique_ptr<mm_model, void (*)(mm_model*)> m(new mm_model(), mm_model_destroy);
-  { const int rc = compile_model(blob, nwords, *m, g_err); if (rc != MM_OK) return rc; }
-  HIPCHK(hipGetDevice(&m->device));
-  HIPCHK(hipMalloc((void**)&m->d_blob, m->words.size() * sizeof(uint32_t)));
-  HIPCHK(hipMemcpy(m->d_blob, m->words.data(), m->words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  { const int rc = upload_consts(m.get()); if (rc != MM_OK) return rc; }
+  std::unique_ptr<mm_model> m(new mm_model());
+  if (int rc = compile_model(blob, nwords, *m, g_err)) return rc;
+  if (int rc = upload_model(m.get())) return rc;
+  if (int rc = upload_consts(m.get())) return rc;
   *out = m.release();
   return MM_OK;
 }
 
-extern "C" void mm_model_destroy(mm_model* m) {
-  std::unique_ptr<mm_model> host(m);   // frees the host object on return
-  if (m && m->d_blob) (void)hipFree(m->d_blob);
-}
+extern "C" void mm_model_destroy(mm_model* m) { delete m; }
 
+// the decisions are the planner's (set_lanes / set_option of myosim_launch_plan.hpp); here: decide, then upload_consts
 extern "C" int mm_model_set_lanes(mm_model* m, int lanes) {
   if (!m) return MM_EARG;
   if (lanes == 0) return MM_OK;
-  if (!check_lanes(m, lanes) || !have_model_kernel(m, lanes))
-    return fail(MM_EARG, "lanes_per_env must be 4/8/16/32/64, >= nbody, nv, njnt, padded nv (and constraint rows), with a compiled kernel");
-  m->lanes = lanes;
-  m->lanes_auto = 0;
-  m->lanes_user = 1;
-  build_layout(m);
+  if (int rc = set_lanes(m, m, lanes, g_err)) return rc;
   return upload_consts(m);
 }
 
 extern "C" int mm_model_set_option(mm_model* m, const char* name, int value) {
   if (!m || !name) return MM_EARG;
-  if (!strcmp(name, "lds_model")) { m->lds_model = value; return MM_OK; }
-  if (!strcmp(name, "waves_per_block")) { m->waves_per_block = value; return MM_OK; }
-  if (!strcmp(name, "precision")) {
-    // MM_PREC_F32 (default): the fp32 kernels.  MM_PREC_F64: fp64 arithmetic, registers and LDS tables; state rows stay fp32 (a
-    // drop-in for every caller).  MM_PREC_F64_STATE: the four state rows of mm_state are fp64 as well.  (include/myosim.h)
-    if (value != MM_PREC_F32 && value != MM_PREC_F64 && value != MM_PREC_F64_STATE) return fail(MM_EARG, "precision: MM_PREC_F32 / MM_PREC_F64 / MM_PREC_F64_STATE");
-    if (value != MM_PREC_F32 && m->rpl == 2) return fail(MM_EUNSUPPORTED, "precision: the two-rows-per-lane kernels (64 < njmax <= 128) are fp32 only");
-    if (value != MM_PREC_F32) {
-      bool any = false;
-      for (int c : {4, 8, 16, 32, 64}) any = any || (check_lanes(m, c) && have_kernel_f64(c, m->nvp, m->d.gen, integ_kernel(m->d.integrator)));
-      if (!any) return fail(MM_EUNSUPPORTED, "precision: no fp64 kernel for this model (compiled: limit-rows-only models with nv <= 24 on Euler; general-row models with nv <= 36 at 64 lanes per env on Euler, 36-wide also implicitfast; no RK4)");
-    }
-    const int old = m->precision;
-    m->precision = value;
-    if (m->lanes_user && !have_model_kernel(m, m->lanes)) { m->precision = old; return fail(MM_EUNSUPPORTED, "precision: no kernel of that family at the pinned lanes_per_env"); }
-    if (!m->lanes_user && !have_model_kernel(m, m->lanes)) {   // default width of the family (a general-row model's default is fixed, not pinned: the fp64 general-row kernels are 64 lanes wide)
-      for (int c : {64, 32, 16, 8, 4}) if (check_lanes(m, c) && have_model_kernel(m, c)) m->lanes = c;
-    }
-    build_layout(m);
-    return upload_consts(m);
-  }
-  // mjOption.iterations / ls_iterations of THIS model handle (the blob's values are the default): the reference's MJX envs overwrite
-  // them after loading the model (envs/myo/mjx/mjx_base_env.py:50-51: spec.option.iterations = 6, ls_iterations = 6)
-  if (!strcmp(name, "iterations") || !strcmp(name, "ls_iterations")) {
-    if (value < 1 || value > 1000) return fail(MM_EARG, "iterations / ls_iterations: 1 ... 1000");
-    if (name[0] == 'i') m->d.iterations = value; else m->d.ls_iterations = value;
-    return upload_consts(m);
-  }
-  if (!strcmp(name, "origin_shift")) {   // 0: the kernel works in raw world coordinates (A/B of the fp32 error study)
-    m->d.ox = value ? m->origin[0] : 0.f; m->d.oy = value ? m->origin[1] : 0.f; m->d.oz = value ? m->origin[2] : 0.f;
-    return upload_consts(m);
-  }
-  return fail(MM_EARG, "unknown option");
+  bool consts_changed = false;
+  if (int rc = set_option(m, m, name, value, consts_changed, g_err)) return rc;
+  return consts_changed ? upload_consts(m) : MM_OK;
 }
 
 // mm_task.fwd_carry: the fp32 Euler kernels of 8 dofs and more (Engine::CARRY), and only where the action reaches nothing but act_dot
@@ -333,55 +285,42 @@ extern "C" void mm_debug_set_dump(float* dev_ptr) { g_dbg = dev_ptr; }
 static unsigned long long* g_prof = nullptr;
 extern "C" void mm_debug_set_prof(unsigned long long* dev_ptr) { g_prof = dev_ptr; }
 
-// mm_model_launch_info: when set, the launch path stops short of the launch and reports the geometry and the kernel's
-// occupancy instead (bench.py prices counters per RESIDENT wave with it)
-struct LaunchInfo { int* out; };
-static thread_local LaunchInfo* g_info = nullptr;
-static int report_kernel(const void* fn, dim3 grid, dim3 block, size_t lds, int lanes, int two_wave, int lm) {
-  int nb = 0;
-  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, (int)block.x, lds));
-  hipFuncAttributes fa;
-  HIPCHK(hipFuncGetAttributes(&fa, fn));
-  int* o = g_info->out;
-  o[MM_LAUNCH_LANES] = lanes; o[MM_LAUNCH_WAVES_PER_BLOCK] = (int)block.x / 64; o[MM_LAUNCH_TWO_WAVE] = two_wave;
-  o[MM_LAUNCH_LDS_MODEL] = lm; o[MM_LAUNCH_LDS_BYTES] = (int)lds; o[MM_LAUNCH_BLOCKS] = (int)grid.x;
-  o[MM_LAUNCH_RESIDENT_BLOCKS_PER_CU] = nb; o[MM_LAUNCH_VGPRS] = fa.numRegs;
-  return MM_OK;
-}
-
-// one kernel instantiation, K0 / K1 = its LM = 0 / LM = 1 variants (model through L2 / staged in LDS)
-template <auto K0, auto K1>
-static int launch_k(const mm_model* m, KArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t st, int lm, int G) {
-  // the dynamic-LDS limit is a per-device attribute of the function: one flag per (device, LM variant) of this instantiation
-  static std::atomic<unsigned> attr_done[2] = {{0u}, {0u}};   // bit d = set on device d (devices >= 32: set on every launch)
-  const void* fn = lm ? (const void*)K1 : (const void*)K0;
+// The kernel of a plan: LM = 0 / LM = 1 variants (model through L2 / staged in LDS) of one instantiation.  The dynamic-LDS limit
+// is a per-device attribute of the function: one flag per (device, LM variant) of the instantiation.
+struct KernelPair { const void* k[2]; std::atomic<unsigned>* attr_done; };   // bit d = set on device d (devices >= 32: set on every launch)
+#define MM_PAIR(K0, K1) { static std::atomic<unsigned> done[2] = {{0u}, {0u}}; kp = KernelPair{{(const void*)(K0), (const void*)(K1)}, done}; }
+static int plan_kernel(const mm_model* m, const LaunchPlan& p, const void** fn) {
+  const int G = p.lanes, rk4 = integ_kernel(m->d.integrator);
+  KernelPair kp{};
+#define MM_MATCH(G_, N_, GN_, RK_) (G == G_ && m->nvp == N_ && m->d.gen == GN_ && rk4 == RK_)
+  if (m->precision != MM_PREC_F32) {
+#define X(G_, N_, GN_, RK_) if MM_MATCH(G_, N_, GN_, RK_) MM_PAIR((mm64::k_engine<G_, N_, false, GN_ != 0, RK_>), (mm64::k_engine<G_, N_, true, GN_ != 0, RK_>))
+    MM_KERNELS_F64(X)
+#undef X
+    if (!kp.k[0]) return fail(MM_EUNSUPPORTED, "no compiled precision-mode kernel for this (lanes_per_env, nv) combination");
+  } else if (p.obs_kernel) {
+#define X(G_, N_, GN_, RK_) if MM_MATCH(G_, N_, GN_, RK_) MM_PAIR((k_engine<G_, N_, false, GN_ != 0, RK_, true>), (k_engine<G_, N_, false, GN_ != 0, RK_, true>))
+    MM_KERNELS_OBS(X)
+#undef X
+  } else if (m->rpl == 2) {
+#define X(G_, N_, GN_, RK_) if MM_MATCH(G_, N_, GN_, RK_) MM_PAIR((k_engine_rows2<N_, false>), (k_engine_rows2<N_, true>))
+    MM_KERNELS_S(X)
+#undef X
+    if (!kp.k[0]) return fail(MM_EUNSUPPORTED, "no compiled two-rows-per-lane kernel for this (lanes_per_env, nv) combination");
+  } else {
+#define X(G_, N_, GN_, RK_) if MM_MATCH(G_, N_, GN_, RK_) MM_PAIR((k_engine<G_, N_, false, GN_ != 0, RK_>), (k_engine<G_, N_, true, GN_ != 0, RK_>))
+    MM_KERNEL_LIST(X)
+#undef X
+  }
+#undef MM_MATCH
+  if (!kp.k[0]) return fail(MM_EUNSUPPORTED, "no compiled kernel for this (lanes_per_env, nv) combination");
+  *fn = kp.k[p.lds_model];
   const unsigned bit = m->device < 32 ? (1u << m->device) : 0u;
-  if (!(attr_done[lm].load(std::memory_order_acquire) & bit) || !bit) {
-    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_done[lm].fetch_or(bit, std::memory_order_release);
+  if (!(kp.attr_done[p.lds_model].load(std::memory_order_acquire) & bit) || !bit) {
+    HIPCHK(hipFuncSetAttribute(*fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    kp.attr_done[p.lds_model].fetch_or(bit, std::memory_order_release);
   }
-  if (g_info) return report_kernel(fn, grid, block, lds, G, a.two_wave, lm);
-  if (lm) hipLaunchKernelGGL(K1, grid, block, lds, st, a);
-  else hipLaunchKernelGGL(K0, grid, block, lds, st, a);
-  HIPCHK(hipGetLastError());
   return MM_OK;
-}
-
-// group width (lanes per env) a launch over `nenv` envs uses: the pinned / default width, or -- for models without general
-// constraint rows, whose LDS tables do not depend on the width -- the narrowest group (most envs per wave) that still yields
-// >= 2 waves per CU, else the widest available
-static int pick_lanes(const mm_model* m, int nenv) {
-  int G = m->lanes;
-  if (m->lanes_auto && !m->d.gen) {
-    int best = 0;
-    for (int c : {4, 8, 16, 32, 64}) {
-      if (!check_lanes(m, c) || !have_model_kernel(m, c)) continue;
-      best = c;
-      if ((nenv + (64 / c) - 1) / (64 / c) >= 512) break;
-    }
-    if (best) G = best;
-  }
-  return G;
 }
 
 extern "C" int mm_model_launch_lanes(const mm_model* m, int nenv) {
@@ -389,143 +328,56 @@ extern "C" int mm_model_launch_lanes(const mm_model* m, int nenv) {
   return pick_lanes(m, nenv);
 }
 
-static int launch_on_device(const mm_model* m, KArgs& a, void* stream, const int G);
-static int launch(const mm_model* m, KArgs& a, void* stream);
-static void fill_common(const mm_model* m, KArgs& a, const mm_state* s);
 // geometry and occupancy of the env-step launch over `nenv` envs (include/myosim.h: MM_LAUNCH_*); nothing is launched
 extern "C" int mm_model_launch_info(const mm_model* m, int nenv, int* out, int nout) {
   if (!m || nenv <= 0 || !out || nout < MM_LAUNCH_COUNT) return fail(MM_EARG, "mm_model_launch_info: bad argument");
-  mm_state s; memset(&s, 0, sizeof(s)); s.nenv = nenv; s.geom_env_id = -1;
-  KArgs a; fill_common(m, a, &s);
-  a.mode = 2;
-  LaunchInfo li{out};
-  g_info = &li;
-  const int rc = launch(m, a, nullptr);
-  g_info = nullptr;
-  return rc;
+  LaunchPlan p;
+  if (int rc = plan_launch(*m, *m, g_two_wave, nenv, false, p, g_err)) return rc;
+  DeviceGuard guard(m->device);
+  if (guard.err != hipSuccess) return fail(MM_EHIP, guard.message());
+  const void* fn = nullptr;
+  if (int rc = plan_kernel(m, p, &fn)) return rc;
+  int nb = 0;
+  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, p.threads, p.lds_bytes));
+  hipFuncAttributes fa;
+  HIPCHK(hipFuncGetAttributes(&fa, fn));
+  out[MM_LAUNCH_LANES] = p.lanes; out[MM_LAUNCH_WAVES_PER_BLOCK] = p.threads / 64; out[MM_LAUNCH_TWO_WAVE] = p.two_wave;
+  out[MM_LAUNCH_LDS_MODEL] = p.lds_model; out[MM_LAUNCH_LDS_BYTES] = (int)p.lds_bytes; out[MM_LAUNCH_BLOCKS] = p.blocks;
+  out[MM_LAUNCH_RESIDENT_BLOCKS_PER_CU] = nb; out[MM_LAUNCH_VGPRS] = fa.numRegs;
+  return MM_OK;
 }
+
+// plan (myosim_launch_plan.hpp), the ConstBlock / Layout of the plan's launch form, the plan's kernel; on the model's device
 static int launch(const mm_model* m, KArgs& a, void* stream) {
   if (a.s.body_pos_env && a.s.body_pos_env_id > 0 && a.s.body_pos_env_id < (int)m->baked_body.size() && m->baked_body[a.s.body_pos_env_id])
     return fail(MM_EUNSUPPORTED, "mm_state.body_pos_env names a body whose frame position is part of a tendon path segment folded into the tendon's "
                                  "constant length at mm_model_create (a segment between two bones that no dof separates)");
-  const int G = pick_lanes(m, a.s.nenv);
-  {   // launch on the model's device (the caller's stream must belong to it); restore the caller's current device afterwards
-    int cur = -1;
-    HIPCHK(hipGetDevice(&cur));
-    if (cur != m->device) {
-      HIPCHK(hipSetDevice(m->device));
-      KArgs& a2 = a;
-      const int rc = launch_on_device(m, a2, stream, G);
-      (void)hipSetDevice(cur);
-      return rc;
-    }
-  }
-  return launch_on_device(m, a, stream, G);
-}
-
-static int launch_on_device(const mm_model* m, KArgs& a, void* stream, const int G) {
-  const int epw = 64 / G;
-  const size_t kLds = 160 * 1024;
-  const size_t blob_bytes = (size_t)((m->blob_words + 3) & ~3) * 4;
-  const int waves_needed = (a.s.nenv + epw - 1) / epw;
-  // lds_model: 1 = stage the model tables in LDS unless that costs resident waves the batch needs (then read them through
-  // L2 instead: a graceful step instead of an occupancy cliff when a model grows past the LDS budget), 0 = never, 2 = always
-  int want = (waves_needed + 255) / 256;       // waves per CU that spread the batch over all 256 CUs in one round
-  if (want < 1) want = 1;
-  if (want > 8) want = 8;
-  // Two waves per env group (Engine::TW): the Euler and implicitfast kernels, when the batch leaves at least half of the
-  // SIMDs without a wave (<= 4 env waves per CU: the block still fits the 512-thread launch bound with the helpers in it) and
-  // the larger per-env tables (a second dense tile) do not cost env waves
-  int two_wave = (g_two_wave && integ_kernel(m->d.integrator) != 1 && want <= 4 && m->waves_per_block <= 0) ? 1 : 0;
-  // precision-mode kernels: a lane's register state doubles, so they are built for one wave per SIMD (256-thread blocks, up to
-  // 512 VGPRs + AGPRs per lane); no helper waves
-  if (m->rpl == 2) two_wave = 0;                // (no helper-wave form of the two-rows-per-lane kernels: Engine::TW)
-  const bool f64 = m->precision != MM_PREC_F32;
-  const int max_wpb = f64 ? 4 : 8;              // __launch_bounds__ of the family
-  if (f64) { two_wave = 0; if (want > max_wpb) want = max_wpb; }
-  // the reset-observation pass of a task (mm_task.obs_only) has its own kernel symbol where one is compiled (model through L2)
-  const bool obs_kernel = m->rpl == 1 && a.mode == 2 && a.t.obs_only && have_obs_kernel(G, m->nvp, m->d.gen, integ_kernel(m->d.integrator));
-  int lm = 0, wpb = 0;
-  size_t per_env = 0, model_bytes = 0;
-  for (;;) {
-    per_env = two_wave ? m->lds_per_env_tw : m->lds_per_env;
-    auto fit_waves = [&](size_t mbytes) {   // waves of one block that fit in LDS next to the model copy (<= 8)
-      int fit = max_wpb;                       // __launch_bounds__ (512 threads; 256 in precision mode)
-      while (fit > 1 && mbytes + (size_t)fit * epw * per_env > kLds) fit--;
-      return fit;
-    };
-    lm = (m->lds_model && !obs_kernel) ? 1 : 0;
-    if (m->lds_model == 1 && fit_waves(blob_bytes) < want && fit_waves(0) > fit_waves(blob_bytes)) lm = 0;
-    if (m->lds_model == 1 && blob_bytes + (size_t)epw * per_env > kLds) lm = 0;   // not even one wave fits next to the model copy
-    model_bytes = lm ? blob_bytes : 0;
-    wpb = std::min(m->waves_per_block, max_wpb);
-    if (wpb <= 0) {
-      // one block per CU sharing one model copy: as many waves as fit in LDS, but no fatter than needed
-      wpb = want;
-      const int fit = fit_waves(model_bytes);
-      if (wpb > fit) wpb = fit;
-    }
-    if (two_wave && (wpb < want || wpb > 4)) { two_wave = 0; continue; }   // the extra tile would cost env waves: one wave per env
-    break;
-  }
-  const int epb = epw * wpb;
-  const size_t lds = model_bytes + (size_t)epb * per_env;
-  if (lds > kLds) return fail(MM_ELDS, "per-block LDS tables exceed 160 KiB");
-  a.two_wave = two_wave;
-  if (two_wave) { a.cofs = m->cofs_tw; a.L = m->Ltw; }
-  dim3 grid((a.s.nenv + epb - 1) / epb), block(64 * wpb * (a.two_wave ? 2 : 1));
-  hipStream_t st = (hipStream_t)stream;
-  a.blob_words = m->blob_words;
+  DeviceGuard guard(m->device);
+  if (guard.err != hipSuccess) return fail(MM_EHIP, guard.message());
+  LaunchPlan p;
+  if (int rc = plan_launch(*m, *m, g_two_wave, a.s.nenv, a.mode == 2 && a.t.obs_only, p, g_err)) return rc;
+  a.two_wave = p.two_wave;
+  if (p.two_wave) { a.cofs = m->cofs_tw; a.L = m->Ltw; }
   a.prof = g_prof;
-  const int rk4 = integ_kernel(m->d.integrator);
   a.state_f64 = m->precision == MM_PREC_F64_STATE ? 1 : 0;
-  if (f64) {
-#define X(G_, N_, GN_, RK_) \
-    if (G == G_ && m->nvp == N_ && m->d.gen == GN_ && rk4 == RK_) return launch_k<mm64::k_engine<G_, N_, false, GN_ != 0, RK_>, mm64::k_engine<G_, N_, true, GN_ != 0, RK_>>(m, a, grid, block, lds, st, lm, G_);
-    MM_KERNELS_F64(X)
-#undef X
-    return fail(MM_EUNSUPPORTED, "no compiled precision-mode kernel for this (lanes_per_env, nv) combination");
-  }
-  if (obs_kernel) {
-#define X(G_, N_, GN_, RK_) \
-    if (G == G_ && m->nvp == N_ && m->d.gen == GN_ && rk4 == RK_) return launch_k<k_engine<G_, N_, false, GN_ != 0, RK_, true>, k_engine<G_, N_, false, GN_ != 0, RK_, true>>(m, a, grid, block, lds, st, 0, G_);
-    MM_KERNELS_OBS(X)
-#undef X
-  }
-  if (m->rpl == 2) {
-#define X(G_, N_, GN_, RK_) \
-    if (G == G_ && m->nvp == N_ && m->d.gen == GN_ && rk4 == RK_) return launch_k<k_engine_rows2<N_, false>, k_engine_rows2<N_, true>>(m, a, grid, block, lds, st, lm, 64);
-    MM_KERNELS_S(X)
-#undef X
-    return fail(MM_EUNSUPPORTED, "no compiled two-rows-per-lane kernel for this (lanes_per_env, nv) combination");
-  }
-#define X(G_, N_, GN_, RK_) \
-  if (G == G_ && m->nvp == N_ && m->d.gen == GN_ && rk4 == RK_) return launch_k<k_engine<G_, N_, false, GN_ != 0, RK_>, k_engine<G_, N_, true, GN_ != 0, RK_>>(m, a, grid, block, lds, st, lm, G_);
-  MM_KERNEL_LIST(X)
-#undef X
-  return fail(MM_EUNSUPPORTED, "no compiled kernel for this (lanes_per_env, nv) combination");
-}
-
-static void fill_common(const mm_model* m, KArgs& a, const mm_state* s) {
-  memset(&a, 0, sizeof(a));
-  a.blob = m->d_blob; a.cofs = m->cofs;
-  memcpy(a.sec, m->sec, sizeof(a.sec));
-  a.d = m->d; a.L = m->L; a.D = m->D; a.x = m->x; a.s = *s;
-  if (!a.s.geom_size_env || a.s.geom_env_id < 0 || a.s.geom_env_id >= m->d.ngeom) { a.s.geom_size_env = nullptr; a.s.geom_type_env = nullptr; a.s.geom_env_id = -1; }
-  if (!a.s.body_mass_env || a.s.body_mass_env_id <= 0 || a.s.body_mass_env_id >= m->d.nbody) { a.s.body_mass_env = nullptr; a.s.body_mass_env_id = -1; }
-  if (!a.s.body_pos_env || a.s.body_pos_env_id <= 0 || a.s.body_pos_env_id >= m->d.nbody) { a.s.body_pos_env = nullptr; a.s.body_pos_env_id = -1; }
+  const void* fn = nullptr;
+  if (int rc = plan_kernel(m, p, &fn)) return rc;
+  void* args[] = {&a};
+  (void)hipLaunchKernel(fn, dim3(p.blocks), dim3(p.threads), args, p.lds_bytes, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return MM_OK;
 }
 
 extern "C" int mm_step(const mm_model* m, const mm_state* s, const float* ctrl, int nsub, void* stream) {
   if (!m || !s || s->nenv <= 0 || nsub < 0) return fail(MM_EARG, "mm_step: bad argument");
-  KArgs a; fill_common(m, a, s);
+  KArgs a; fill_kargs(a, m, s);
   a.ctrl = ctrl; a.mode = 0; a.t.nsubsteps = nsub; a.dbg = nullptr;
   return launch(m, a, stream);
 }
 
 extern "C" int mm_forward(const mm_model* m, const mm_state* s, const float* ctrl, const mm_derived* out, void* stream) {
   if (!m || !s || s->nenv <= 0) return fail(MM_EARG, "mm_forward: bad argument");
-  KArgs a; fill_common(m, a, s);
+  KArgs a; fill_kargs(a, m, s);
   a.ctrl = ctrl; a.mode = 1;
   if (out) { a.o = *out; a.has_derived = 1; }
   a.dbg = g_dbg;
@@ -585,7 +437,7 @@ extern "C" int mm_env_step(const mm_model* m, const mm_state* s, const float* ac
   { const int rc = sized_copy(&tt, t, offsetof(mm_task, obs_only) + sizeof(int), "mm_env_step: null task"); if (rc != MM_OK) return rc; }
   t = &tt;
   { const int rc = check_task(m, s, t); if (rc != MM_OK) return rc; }
-  KArgs a; fill_common(m, a, s);
+  KArgs a; fill_kargs(a, m, s);
   a.ctrl = action; a.mode = 2; a.t = *t;
   if (out) { a.o = *out; a.has_derived = 1; }
   a.dbg = g_dbg;
@@ -621,22 +473,32 @@ extern "C" int mm_rollout_step(const mm_model* m, const mm_state* s, const mm_ta
       if (t->fatigue && (!t->fat_MA || !t->fat_MR || !t->fat_MF)) return fail(MM_EARG, "mm_rollout_step: fatigue state missing");
     } else return fail(MM_EUNSUPPORTED, "mm_rollout_step: the folded auto-reset exists for the POSE, WALK and REORIENT tasks (reset the others through reset_mask)");
   }
-  KArgs a; fill_common(m, a, s);
+  KArgs a; fill_kargs(a, m, s);
   a.ctrl = r->action; a.mode = 2; a.t = *t; a.ro = *r; a.has_ro = 1;
   if (out) { a.o = *out; a.has_derived = 1; }
   a.dbg = g_dbg;
   return launch(m, a, stream);
 }
 
+// what every reset entry sets: the model's tables, the state, the mask and the episode bookkeeping; the entry adds its own fields
+static ResetArgs reset_args(const mm_model* m, const mm_state* s, const uint8_t* mask, int32_t* episode, int32_t* step_count, uint64_t seed) {
+  ResetArgs r; memset(&r, 0, sizeof(r));
+  r.blob = m->d_blob; r.state_f64 = m->precision == MM_PREC_F64_STATE; r.qpos0_off = m->sec[MM_SEC_QPOS0]; r.nq = m->d.nq; r.nv = m->d.nv; r.na = m->d.na;
+  r.nenv = s->nenv; r.s = *s; r.mask = mask; r.episode = episode; r.step_count = step_count; r.seed = seed;
+  return r;
+}
+static int launch_reset(const ResetArgs& r, void* stream) {
+  hipLaunchKernelGGL(k_reset, dim3((r.nenv + 255) / 256), dim3(256), 0, (hipStream_t)stream, r);
+  HIPCHK(hipGetLastError());
+  return MM_OK;
+}
+
 extern "C" int mm_reset(const mm_model* m, const mm_state* s, const uint8_t* mask, const float* qpos_src,
                         const float* qvel_src, void* stream) {
   if (!m || !s || s->nenv <= 0) return fail(MM_EARG, "mm_reset: bad argument");
-  ResetArgs r; memset(&r, 0, sizeof(r));
-  r.blob = m->d_blob; r.state_f64 = m->precision == MM_PREC_F64_STATE; r.qpos0_off = m->sec[MM_SEC_QPOS0]; r.nq = m->d.nq; r.nv = m->d.nv; r.na = m->d.na;
-  r.nenv = s->nenv; r.s = *s; r.mask = mask; r.qpos_src = qpos_src; r.qvel_src = qvel_src;
-  hipLaunchKernelGGL(k_reset, dim3((s->nenv + 255) / 256), dim3(256), 0, (hipStream_t)stream, r);
-  HIPCHK(hipGetLastError());
-  return MM_OK;
+  ResetArgs r = reset_args(m, s, mask, nullptr, nullptr, 0);
+  r.qpos_src = qpos_src; r.qvel_src = qvel_src;
+  return launch_reset(r, stream);
 }
 
 extern "C" int mm_pose_reset(const mm_model* m, const mm_state* s, const uint8_t* mask, const float* qlo,
@@ -645,15 +507,10 @@ extern "C" int mm_pose_reset(const mm_model* m, const mm_state* s, const uint8_t
                              int obs_layout, void* stream) {
   if (!m || !s || s->nenv <= 0 || !tlo || !thi || !target) return fail(MM_EARG, "mm_pose_reset: bad argument");
   if (random_qpos && (!qlo || !qhi)) return fail(MM_EARG, "mm_pose_reset: random_qpos needs qlo/qhi");
-  ResetArgs r; memset(&r, 0, sizeof(r));
-  r.blob = m->d_blob; r.state_f64 = m->precision == MM_PREC_F64_STATE; r.qpos0_off = m->sec[MM_SEC_QPOS0]; r.nq = m->d.nq; r.nv = m->d.nv; r.na = m->d.na;
-  r.nenv = s->nenv; r.s = *s; r.mask = mask;
-  r.qlo = qlo; r.qhi = qhi; r.tlo = tlo; r.thi = thi; r.target = target; r.episode = episode;
-  r.step_count = step_count; r.seed = seed; r.pose = 1; r.random_qpos = random_qpos;
+  ResetArgs r = reset_args(m, s, mask, episode, step_count, seed);
+  r.qlo = qlo; r.qhi = qhi; r.tlo = tlo; r.thi = thi; r.target = target; r.pose = 1; r.random_qpos = random_qpos;
   r.obs = obs; r.obs_dim = obs_dim; r.obs_layout = obs_layout;
-  hipLaunchKernelGGL(k_reset, dim3((s->nenv + 255) / 256), dim3(256), 0, (hipStream_t)stream, r);
-  HIPCHK(hipGetLastError());
-  return MM_OK;
+  return launch_reset(r, stream);
 }
 
 extern "C" int mm_uniform_at(float* out, size_t n, uint64_t seed, uint64_t stream_id, size_t first_index, void* stream) {
@@ -768,14 +625,10 @@ extern "C" int mm_reach_reset(const mm_model* m, const mm_state* s, const uint8_
                               float* target, const float* tip0, int ntip, int32_t* episode, int32_t* step_count,
                               uint64_t seed, float* obs, int obs_dim, void* stream) {
   if (!m || !s || s->nenv <= 0 || !tlo || !thi || !target || !tip0 || ntip <= 0) return fail(MM_EARG, "mm_reach_reset: bad argument");
-  ResetArgs r; memset(&r, 0, sizeof(r));
-  r.blob = m->d_blob; r.state_f64 = m->precision == MM_PREC_F64_STATE; r.qpos0_off = m->sec[MM_SEC_QPOS0]; r.nq = m->d.nq; r.nv = m->d.nv; r.na = m->d.na;
-  r.nenv = s->nenv; r.s = *s; r.mask = mask;
-  r.tlo = tlo; r.thi = thi; r.target = target; r.episode = episode; r.step_count = step_count; r.seed = seed;
+  ResetArgs r = reset_args(m, s, mask, episode, step_count, seed);
+  r.tlo = tlo; r.thi = thi; r.target = target;
   r.reach = 1; r.ntip = ntip; r.tip0 = tip0; r.obs = obs; r.obs_dim = obs_dim;
-  hipLaunchKernelGGL(k_reset, dim3((s->nenv + 255) / 256), dim3(256), 0, (hipStream_t)stream, r);
-  HIPCHK(hipGetLastError());
-  return MM_OK;
+  return launch_reset(r, stream);
 }
 
 extern "C" int mm_walk_reset(const mm_model* m, const mm_state* s, const uint8_t* mask, const float* key_a_qpos,
@@ -783,47 +636,38 @@ extern "C" int mm_walk_reset(const mm_model* m, const mm_state* s, const uint8_t
                              int32_t* episode, int32_t* step_count, uint64_t seed, void* stream) {
   if (!m || !s || s->nenv <= 0 || !key_a_qpos || !key_a_qvel) return fail(MM_EARG, "mm_walk_reset: bad argument");
   if (random && (!key_b_qpos || !key_b_qvel)) return fail(MM_EARG, "mm_walk_reset: random reset needs the second key");
-  ResetArgs r; memset(&r, 0, sizeof(r));
-  r.blob = m->d_blob; r.state_f64 = m->precision == MM_PREC_F64_STATE; r.qpos0_off = m->sec[MM_SEC_QPOS0]; r.nq = m->d.nq; r.nv = m->d.nv; r.na = m->d.na;
-  r.nenv = s->nenv; r.s = *s; r.mask = mask; r.episode = episode; r.step_count = step_count; r.seed = seed;
+  ResetArgs r = reset_args(m, s, mask, episode, step_count, seed);
   r.walk = 1; r.walk_random = random; r.ka_qpos = key_a_qpos; r.ka_qvel = key_a_qvel; r.kb_qpos = key_b_qpos; r.kb_qvel = key_b_qvel;
-  hipLaunchKernelGGL(k_reset, dim3((s->nenv + 255) / 256), dim3(256), 0, (hipStream_t)stream, r);
-  HIPCHK(hipGetLastError());
-  return MM_OK;
+  return launch_reset(r, stream);
+}
+
+// geom_type_env non-null: also draw the object type (size tables [4][ntab][3]); mm_reorient_reset is the call without one
+static int reorient_reset(const char* bad, const mm_model* m, const mm_state* s, const uint8_t* mask, const float* init_qpos,
+                          const float* size_tables, int ntab, float* geom_size_env, int32_t* geom_type_env, float* axis_half, float* des_rot,
+                          float tar_length, int32_t* episode, int32_t* step_count, uint64_t seed, void* stream) {
+  if (!m || !s || s->nenv <= 0 || !init_qpos || !size_tables || ntab <= 0 || !geom_size_env || !axis_half || !des_rot || !(tar_length > 0.f))
+    return fail(MM_EARG, bad);
+  ResetArgs r = reset_args(m, s, mask, episode, step_count, seed);
+  r.qpos_bcast = init_qpos;
+  r.reor = 1; r.reor_ntab = ntab; r.reor_tab = size_tables; r.reor_gsize = geom_size_env; r.reor_axis_half = axis_half;
+  r.reor_des_rot = des_rot; r.reor_tar_length = tar_length; r.reor_gtype = geom_type_env;
+  return launch_reset(r, stream);
 }
 
 extern "C" int mm_reorient_reset(const mm_model* m, const mm_state* s, const uint8_t* mask, const float* init_qpos,
                                  const float* size_table, int ntab, float* geom_size_env, float* axis_half, float* des_rot,
                                  float tar_length, int32_t* episode, int32_t* step_count, uint64_t seed, void* stream) {
-  if (!m || !s || s->nenv <= 0 || !init_qpos || !size_table || ntab <= 0 || !geom_size_env || !axis_half || !des_rot || !(tar_length > 0.f))
-    return fail(MM_EARG, "mm_reorient_reset: bad argument");
-  ResetArgs r; memset(&r, 0, sizeof(r));
-  r.blob = m->d_blob; r.state_f64 = m->precision == MM_PREC_F64_STATE; r.qpos0_off = m->sec[MM_SEC_QPOS0]; r.nq = m->d.nq; r.nv = m->d.nv; r.na = m->d.na;
-  r.nenv = s->nenv; r.s = *s; r.mask = mask; r.episode = episode; r.step_count = step_count; r.seed = seed;
-  r.qpos_bcast = init_qpos;
-  r.reor = 1; r.reor_ntab = ntab; r.reor_tab = size_table; r.reor_gsize = geom_size_env; r.reor_axis_half = axis_half;
-  r.reor_des_rot = des_rot; r.reor_tar_length = tar_length;
-  hipLaunchKernelGGL(k_reset, dim3((s->nenv + 255) / 256), dim3(256), 0, (hipStream_t)stream, r);
-  HIPCHK(hipGetLastError());
-  return MM_OK;
+  return reorient_reset("mm_reorient_reset: bad argument", m, s, mask, init_qpos, size_table, ntab, geom_size_env, nullptr, axis_half, des_rot,
+                        tar_length, episode, step_count, seed, stream);
 }
 
 extern "C" int mm_reorient_reset_typed(const mm_model* m, const mm_state* s, const uint8_t* mask, const float* init_qpos,
                                        const float* size_tables, int ntab, float* geom_size_env, int32_t* geom_type_env,
                                        float* axis_half, float* des_rot, float tar_length, int32_t* episode,
                                        int32_t* step_count, uint64_t seed, void* stream) {
-  if (!m || !s || s->nenv <= 0 || !init_qpos || !size_tables || ntab <= 0 || !geom_size_env || !geom_type_env || !axis_half || !des_rot ||
-      !(tar_length > 0.f))
-    return fail(MM_EARG, "mm_reorient_reset_typed: bad argument");
-  ResetArgs r; memset(&r, 0, sizeof(r));
-  r.blob = m->d_blob; r.state_f64 = m->precision == MM_PREC_F64_STATE; r.qpos0_off = m->sec[MM_SEC_QPOS0]; r.nq = m->d.nq; r.nv = m->d.nv; r.na = m->d.na;
-  r.nenv = s->nenv; r.s = *s; r.mask = mask; r.episode = episode; r.step_count = step_count; r.seed = seed;
-  r.qpos_bcast = init_qpos;
-  r.reor = 1; r.reor_ntab = ntab; r.reor_tab = size_tables; r.reor_gsize = geom_size_env; r.reor_axis_half = axis_half;
-  r.reor_des_rot = des_rot; r.reor_tar_length = tar_length; r.reor_gtype = geom_type_env;
-  hipLaunchKernelGGL(k_reset, dim3((s->nenv + 255) / 256), dim3(256), 0, (hipStream_t)stream, r);
-  HIPCHK(hipGetLastError());
-  return MM_OK;
+  if (!geom_type_env) return fail(MM_EARG, "mm_reorient_reset_typed: bad argument");
+  return reorient_reset("mm_reorient_reset_typed: bad argument", m, s, mask, init_qpos, size_tables, ntab, geom_size_env, geom_type_env, axis_half,
+                        des_rot, tar_length, episode, step_count, seed, stream);
 }
 
 extern "C" int mm_pen_reset(const mm_model* m, const mm_state* s, const uint8_t* mask, const float* init_qpos, float axis_half,
@@ -831,28 +675,20 @@ extern "C" int mm_pen_reset(const mm_model* m, const mm_state* s, const uint8_t*
                             int32_t* step_count, uint64_t seed, void* stream) {
   if (!m || !s || s->nenv <= 0 || !init_qpos || !des_rot || !(tar_length > 0.f) || !(axis_half > 0.f))
     return fail(MM_EARG, "mm_pen_reset: bad argument");
-  ResetArgs r; memset(&r, 0, sizeof(r));
-  r.blob = m->d_blob; r.state_f64 = m->precision == MM_PREC_F64_STATE; r.qpos0_off = m->sec[MM_SEC_QPOS0]; r.nq = m->d.nq; r.nv = m->d.nv; r.na = m->d.na;
-  r.nenv = s->nenv; r.s = *s; r.mask = mask; r.episode = episode; r.step_count = step_count; r.seed = seed;
+  ResetArgs r = reset_args(m, s, mask, episode, step_count, seed);
   r.qpos_bcast = init_qpos;
   r.reor = 1; r.pen = 1; r.pen_axis_half = axis_half; r.pen_lo0 = lo0; r.pen_hi0 = hi0; r.pen_lo1 = lo1; r.pen_hi1 = hi1;
   r.reor_des_rot = des_rot; r.reor_tar_length = tar_length;
-  hipLaunchKernelGGL(k_reset, dim3((s->nenv + 255) / 256), dim3(256), 0, (hipStream_t)stream, r);
-  HIPCHK(hipGetLastError());
-  return MM_OK;
+  return launch_reset(r, stream);
 }
 
 extern "C" int mm_objhold_reset(const mm_model* m, const mm_state* s, const uint8_t* mask, const float* init_qpos,
                                 const float* goal_center, float goal_half, float size_lo, float size_hi, float* goal,
                                 float* geom_size_env, int32_t* episode, int32_t* step_count, uint64_t seed, void* stream) {
   if (!m || !s || s->nenv <= 0 || !init_qpos || !goal_center || !goal) return fail(MM_EARG, "mm_objhold_reset: bad argument");
-  ResetArgs r; memset(&r, 0, sizeof(r));
-  r.blob = m->d_blob; r.state_f64 = m->precision == MM_PREC_F64_STATE; r.qpos0_off = m->sec[MM_SEC_QPOS0]; r.nq = m->d.nq; r.nv = m->d.nv; r.na = m->d.na;
-  r.nenv = s->nenv; r.s = *s; r.mask = mask; r.episode = episode; r.step_count = step_count; r.seed = seed;
+  ResetArgs r = reset_args(m, s, mask, episode, step_count, seed);
   r.qpos_bcast = init_qpos;
   r.hold = 1; r.hold_center = goal_center; r.hold_half = goal_half; r.hold_slo = size_lo; r.hold_shi = size_hi;
   r.hold_goal = goal; r.hold_gsize = geom_size_env;
-  hipLaunchKernelGGL(k_reset, dim3((s->nenv + 255) / 256), dim3(256), 0, (hipStream_t)stream, r);
-  HIPCHK(hipGetLastError());
-  return MM_OK;
+  return launch_reset(r, stream);
 }

@@ -1,0 +1,147 @@
+#pragma once
+// myosim_launch_plan.hpp -- the host-only launch planner: ModelImage + launch options + batch size -> the geometry of a launch, and
+// the pure halves of mm_model_set_lanes / mm_model_set_option (which width, precision and iteration counts a call leaves in the
+// image, or which refusal it gives).  Standard library only (no HIP), like myosim_model_compile.hpp: the engine and the inverse
+// library (myosim_engine.hip, inverse/myosim_inverse.hip) dispatch on the plan, mm_model_launch_info reports it, and a plain host
+// build (tests/tools/launch_plan_main.cpp) runs the same code under the host sanitizers.
+#include "myosim_model_compile.hpp"
+
+// what a model handle holds besides the image and its device copy (mm_model_set_lanes / mm_model_set_option)
+struct LaunchOptions {
+  int lanes_user = 0;        // the width was pinned by the caller (mm_model_set_lanes), not chosen as the model's default
+  int waves_per_block = 0;   // 0 = auto
+  int lds_model = 1;         // 1 = stage the model tables in LDS unless that costs resident waves the batch needs, 0 = never, 2 = always
+};
+
+struct LaunchPlan {
+  int lanes;             // lanes per env (pick_lanes)
+  int waves_per_block;   // env waves of a block (the helper waves of a two-wave launch come on top)
+  int two_wave;          // every env group has a helper wave (Engine::TW): ConstBlock / Layout of the two-wave form
+  int lds_model;         // the block stages the model tables in LDS (LM = 1 variant), else reads them through L2
+  size_t lds_bytes;      // dynamic LDS of a block
+  int blocks, threads;   // grid and block size
+  bool obs_kernel;       // the reset-observation pass of a task runs its own kernel symbol (MM_KERNELS_OBS)
+};
+
+// group width (lanes per env) a launch over `nenv` envs uses: the pinned / default width, or -- for models without general
+// constraint rows, whose LDS tables do not depend on the width -- the narrowest group (most envs per wave) that still yields
+// >= 2 waves per CU, else the widest available
+static inline int pick_lanes(const ModelImage* m, int nenv) {
+  int G = m->lanes;
+  if (m->lanes_auto && !m->d.gen) {
+    int best = 0;
+    for (int c : {4, 8, 16, 32, 64}) {
+      if (!check_lanes(m, c) || !have_model_kernel(m, c)) continue;
+      best = c;
+      if ((nenv + (64 / c) - 1) / (64 / c) >= 512) break;
+    }
+    if (best) G = best;
+  }
+  return G;
+}
+
+// The launch over `nenv` envs: MM_OK and the plan, or MM_ELDS with the reason in `err`.  two_wave_on: the MYOSIM_TWO_WAVE switch
+// (0 switches the helper waves off); obs_only: the pass is a task's reset-observation pass (mm_task.obs_only of an env-step).
+static inline int plan_launch(const ModelImage& m, const LaunchOptions& opt, int two_wave_on, int nenv, bool obs_only, LaunchPlan& p,
+                              std::string& err) {
+  const int G = pick_lanes(&m, nenv);
+  const int epw = 64 / G;
+  const size_t kLds = 160 * 1024;
+  const size_t blob_bytes = (size_t)((m.blob_words + 3) & ~3) * 4;
+  const int waves_needed = (nenv + epw - 1) / epw;
+  // lds_model: 1 = stage the model tables in LDS unless that costs resident waves the batch needs (then read them through
+  // L2 instead: a graceful step instead of an occupancy cliff when a model grows past the LDS budget), 0 = never, 2 = always
+  int want = (waves_needed + 255) / 256;       // waves per CU that spread the batch over all 256 CUs in one round
+  if (want < 1) want = 1;
+  if (want > 8) want = 8;
+  // Two waves per env group (Engine::TW): the Euler and implicitfast kernels, when the batch leaves at least half of the
+  // SIMDs without a wave (<= 4 env waves per CU: the block still fits the 512-thread launch bound with the helpers in it) and
+  // the larger per-env tables (a second dense tile) do not cost env waves
+  int two_wave = (two_wave_on && integ_kernel(m.d.integrator) != 1 && want <= 4 && opt.waves_per_block <= 0) ? 1 : 0;
+  // precision-mode kernels: a lane's register state doubles, so they are built for one wave per SIMD (256-thread blocks, up to
+  // 512 VGPRs + AGPRs per lane); no helper waves
+  if (m.rpl == 2) two_wave = 0;                 // (no helper-wave form of the two-rows-per-lane kernels: Engine::TW)
+  const bool f64 = m.precision != MM_PREC_F32;
+  const int max_wpb = f64 ? 4 : 8;              // __launch_bounds__ of the family
+  if (f64) { two_wave = 0; if (want > max_wpb) want = max_wpb; }
+  // the reset-observation pass of a task (mm_task.obs_only) has its own kernel symbol where one is compiled (model through L2)
+  const bool obs_kernel = m.rpl == 1 && obs_only && have_obs_kernel(G, m.nvp, m.d.gen, integ_kernel(m.d.integrator));
+  int lm = 0, wpb = 0;
+  size_t per_env = 0, model_bytes = 0;
+  for (;;) {
+    per_env = two_wave ? m.lds_per_env_tw : m.lds_per_env;
+    auto fit_waves = [&](size_t mbytes) {   // waves of one block that fit in LDS next to the model copy (<= 8)
+      int fit = max_wpb;                       // __launch_bounds__ (512 threads; 256 in precision mode)
+      while (fit > 1 && mbytes + (size_t)fit * epw * per_env > kLds) fit--;
+      return fit;
+    };
+    lm = (opt.lds_model && !obs_kernel) ? 1 : 0;
+    if (opt.lds_model == 1 && fit_waves(blob_bytes) < want && fit_waves(0) > fit_waves(blob_bytes)) lm = 0;
+    if (opt.lds_model == 1 && blob_bytes + (size_t)epw * per_env > kLds) lm = 0;   // not even one wave fits next to the model copy
+    model_bytes = lm ? blob_bytes : 0;
+    wpb = std::min(opt.waves_per_block, max_wpb);
+    if (wpb <= 0) {
+      // one block per CU sharing one model copy: as many waves as fit in LDS, but no fatter than needed
+      wpb = want;
+      const int fit = fit_waves(model_bytes);
+      if (wpb > fit) wpb = fit;
+    }
+    if (two_wave && (wpb < want || wpb > 4)) { two_wave = 0; continue; }   // the extra tile would cost env waves: one wave per env
+    break;
+  }
+  const int epb = epw * wpb;
+  const size_t lds = model_bytes + (size_t)epb * per_env;
+  if (lds > kLds) return mmc::refuse(err, MM_ELDS, "per-block LDS tables exceed 160 KiB");
+  p = LaunchPlan{G, wpb, two_wave, lm, lds, (nenv + epb - 1) / epb, 64 * wpb * (two_wave ? 2 : 1), obs_kernel};
+  return MM_OK;
+}
+
+// mm_model_set_lanes short of the upload: the width pinned and the image laid out again, or the refusal
+static inline int set_lanes(ModelImage* m, LaunchOptions* opt, int lanes, std::string& err) {
+  if (!check_lanes(m, lanes) || !have_model_kernel(m, lanes))
+    return mmc::refuse(err, MM_EARG, "lanes_per_env must be 4/8/16/32/64, >= nbody, nv, njnt, padded nv (and constraint rows), with a compiled kernel");
+  m->lanes = lanes;
+  m->lanes_auto = 0;
+  opt->lanes_user = 1;
+  build_layout(m);
+  return MM_OK;
+}
+
+// mm_model_set_option short of the upload; consts_changed: the ConstBlocks of the image have to be written and sent again
+static inline int set_option(ModelImage* m, LaunchOptions* opt, const char* name, int value, bool& consts_changed, std::string& err) {
+  consts_changed = false;
+  if (!strcmp(name, "lds_model")) { opt->lds_model = value; return MM_OK; }
+  if (!strcmp(name, "waves_per_block")) { opt->waves_per_block = value; return MM_OK; }
+  consts_changed = true;
+  if (!strcmp(name, "precision")) {
+    // MM_PREC_F32 (default): the fp32 kernels.  MM_PREC_F64: fp64 arithmetic, registers and LDS tables; state rows stay fp32 (a
+    // drop-in for every caller).  MM_PREC_F64_STATE: the four state rows of mm_state are fp64 as well.  (include/myosim.h)
+    if (value != MM_PREC_F32 && value != MM_PREC_F64 && value != MM_PREC_F64_STATE) return mmc::refuse(err, MM_EARG, "precision: MM_PREC_F32 / MM_PREC_F64 / MM_PREC_F64_STATE");
+    if (value != MM_PREC_F32 && m->rpl == 2) return mmc::refuse(err, MM_EUNSUPPORTED, "precision: the two-rows-per-lane kernels (64 < njmax <= 128) are fp32 only");
+    if (value != MM_PREC_F32) {
+      bool any = false;
+      for (int c : {4, 8, 16, 32, 64}) any = any || (check_lanes(m, c) && have_kernel_f64(c, m->nvp, m->d.gen, integ_kernel(m->d.integrator)));
+      if (!any) return mmc::refuse(err, MM_EUNSUPPORTED, "precision: no fp64 kernel for this model (compiled: limit-rows-only models with nv <= 24 on Euler; general-row models with nv <= 36 at 64 lanes per env on Euler, 36-wide also implicitfast; no RK4)");
+    }
+    const int old = m->precision;
+    m->precision = value;
+    if (opt->lanes_user && !have_model_kernel(m, m->lanes)) { m->precision = old; return mmc::refuse(err, MM_EUNSUPPORTED, "precision: no kernel of that family at the pinned lanes_per_env"); }
+    if (!opt->lanes_user && !have_model_kernel(m, m->lanes)) {   // default width of the family (a general-row model's default is fixed, not pinned: the fp64 general-row kernels are 64 lanes wide)
+      for (int c : {64, 32, 16, 8, 4}) if (check_lanes(m, c) && have_model_kernel(m, c)) m->lanes = c;
+    }
+    build_layout(m);
+    return MM_OK;
+  }
+  // mjOption.iterations / ls_iterations of THIS model handle (the blob's values are the default): the reference's MJX envs overwrite
+  // them after loading the model (envs/myo/mjx/mjx_base_env.py:50-51: spec.option.iterations = 6, ls_iterations = 6)
+  if (!strcmp(name, "iterations") || !strcmp(name, "ls_iterations")) {
+    if (value < 1 || value > 1000) return mmc::refuse(err, MM_EARG, "iterations / ls_iterations: 1 ... 1000");
+    if (name[0] == 'i') m->d.iterations = value; else m->d.ls_iterations = value;
+    return MM_OK;
+  }
+  if (!strcmp(name, "origin_shift")) {   // 0: the kernel works in raw world coordinates (A/B of the fp32 error study)
+    m->d.ox = value ? m->origin[0] : 0.f; m->d.oy = value ? m->origin[1] : 0.f; m->d.oz = value ? m->origin[2] : 0.f;
+    return MM_OK;
+  }
+  return mmc::refuse(err, MM_EARG, "unknown option");
+}

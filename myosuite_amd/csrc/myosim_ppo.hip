@@ -19,21 +19,19 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <algorithm>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/myosim.h"
 #include "../../include/myosim_ppo.h"
 
-namespace {
+static thread_local std::string g_perr;
+static int pfail(int code, const std::string& msg) { g_perr = msg; return code; }
+#define MM_HOST_FAIL pfail
+#include "myosim_host.hpp"
 
-thread_local std::string g_perr;
-int pfail(int code, const std::string& msg) { g_perr = msg; return code; }
-#define PHIPCHK(x)                                                                                  \
-  do {                                                                                              \
-    hipError_t e_ = (x);                                                                            \
-    if (e_ != hipSuccess) return pfail(MM_EHIP, std::string(#x) + ": " + hipGetErrorString(e_));    \
-  } while (0)
+namespace {
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
@@ -571,13 +569,6 @@ struct mm_ppo {
 
 extern "C" const char* mm_ppo_last_error(void) { return g_perr.c_str(); }
 
-// the launches of a handle go to ITS device (workspace, descriptors), whatever device is current in the calling thread
-struct DeviceGuard {
-  int prev = -1;
-  explicit DeviceGuard(int dev) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; if (prev != dev) (void)hipSetDevice(dev); else prev = -1; }
-  ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
 extern "C" void mm_ppo_destroy(mm_ppo* h) {
   if (!h) return;
   for (void* p : {(void*)h->dnet, (void*)h->part, (void*)h->m1, (void*)h->m2, (void*)h->blocksq, (void*)h->step}) (void)hipFree(p);
@@ -606,48 +597,44 @@ extern "C" int mm_ppo_create(const mm_ppo_config* c, int device, mm_ppo** out) {
   if (c->vf_layers < 1 || c->vf_layers > MM_PPO_MAX_LAYERS || c->vf_widths[c->vf_layers - 1] != 1) return pfail(MM_EARG, "mm_ppo_create: the value network's last layer must have 1 output");
   if (c->squash != MM_PPO_SQUASH_TANH && c->squash != MM_PPO_SQUASH_SIGMOID) return pfail(MM_EARG, "mm_ppo_create: squash");
   if (c->max_minibatch < 1) return pfail(MM_EARG, "mm_ppo_create: max_minibatch");
-  mm_ppo* h = new mm_ppo();
+  std::unique_ptr<mm_ppo, void (*)(mm_ppo*)> h(new mm_ppo(), mm_ppo_destroy);
   h->cfg = *c; h->device = device;
   int rc;
   for (int r = 0; r < 2; r++) {
-    if ((rc = fill_net(h->net[0][r], c->obs_dim, c->pi_layers, c->pi_widths, "policy")) || (rc = fill_net(h->net[1][r], c->obs_dim, c->vf_layers, c->vf_widths, "value"))) { delete h; return rc; }
+    if ((rc = fill_net(h->net[0][r], c->obs_dim, c->pi_layers, c->pi_widths, "policy")) || (rc = fill_net(h->net[1][r], c->obs_dim, c->vf_layers, c->vf_widths, "value"))) return rc;
     plan(h->net[0][r], 16 * (r + 1), 2 * c->act_dim); plan(h->net[1][r], 16 * (r + 1), 0);      // raw actions + the entropy sample's noise rows
     h->lds[r] = sizeof(float) * (size_t)std::max(h->net[0][r].total, h->net[1][r].total);
   }
   h->np_pi = h->net[0][0].npar; h->np_vf = h->net[1][0].npar; h->np = h->np_pi + h->np_vf;
   const size_t lds_limit = 150 * 1024;       // 160 KB per CU minus the kernels' static arrays (descriptor, row indices, per-sample scalars) and a margin
-  if (h->lds[0] > lds_limit) { const size_t need = h->lds[0]; delete h; return pfail(MM_ELDS, "mm_ppo_create: a 16-sample workgroup needs " + std::to_string(need) + " B of LDS"); }
+  if (h->lds[0] > lds_limit) { const size_t need = h->lds[0]; return pfail(MM_ELDS, "mm_ppo_create: a 16-sample workgroup needs " + std::to_string(need) + " B of LDS"); }
   h->max_rt = h->lds[1] <= lds_limit ? 2 : 1;
   if (const char* e = getenv("MYOSIM_PPO_SAMPLES")) h->force_rt = atoi(e) == 32 ? 2 : atoi(e) == 16 ? 1 : 0;
-  int cur = 0;
-  (void)hipGetDevice(&cur);
-#define CREATE_CHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { std::string m_ = std::string(#x) + ": " + hipGetErrorString(e_); (void)hipSetDevice(cur); mm_ppo_destroy(h); return pfail(MM_EHIP, m_); } } while (0)
-  CREATE_CHK(hipSetDevice(device));
-  CREATE_CHK(hipMalloc(&h->dnet, 4 * sizeof(NetD)));
-  CREATE_CHK(hipMemcpy(h->dnet, &h->net[0][0], 4 * sizeof(NetD), hipMemcpyHostToDevice));
+  DeviceGuard guard(device, "hipSetDevice(device)");   // (a failure below: the guard restores the caller's device, then h is destroyed)
+  if (guard.err != hipSuccess) return pfail(MM_EHIP, guard.message());
+  HIPCHK(hipMalloc(&h->dnet, 4 * sizeof(NetD)));
+  HIPCHK(hipMemcpy(h->dnet, &h->net[0][0], 4 * sizeof(NetD), hipMemcpyHostToDevice));
   h->nb_max = (c->max_minibatch + 15) / 16;
-  CREATE_CHK(hipMalloc(&h->part, sizeof(float) * (size_t)h->nb_max * h->np));
+  HIPCHK(hipMalloc(&h->part, sizeof(float) * (size_t)h->nb_max * h->np));
   h->nbq = (h->np + RED_P - 1) / RED_P;          // workgroups of k_ppo_reduce / k_ppo_sumsq = entries of blocksq
-  CREATE_CHK(hipMalloc(&h->m1, sizeof(float) * h->np)); CREATE_CHK(hipMalloc(&h->m2, sizeof(float) * h->np));
-  CREATE_CHK(hipMalloc(&h->blocksq, sizeof(float) * h->nbq)); CREATE_CHK(hipMalloc(&h->step, 2 * sizeof(float)));
-  CREATE_CHK(hipMemset(h->m1, 0, sizeof(float) * h->np)); CREATE_CHK(hipMemset(h->m2, 0, sizeof(float) * h->np));
-  CREATE_CHK(hipMemset(h->blocksq, 0, sizeof(float) * h->nbq)); CREATE_CHK(hipMemset(h->step, 0, 2 * sizeof(float)));
+  HIPCHK(hipMalloc(&h->m1, sizeof(float) * h->np)); HIPCHK(hipMalloc(&h->m2, sizeof(float) * h->np));
+  HIPCHK(hipMalloc(&h->blocksq, sizeof(float) * h->nbq)); HIPCHK(hipMalloc(&h->step, 2 * sizeof(float)));
+  HIPCHK(hipMemset(h->m1, 0, sizeof(float) * h->np)); HIPCHK(hipMemset(h->m2, 0, sizeof(float) * h->np));
+  HIPCHK(hipMemset(h->blocksq, 0, sizeof(float) * h->nbq)); HIPCHK(hipMemset(h->step, 0, 2 * sizeof(float)));
   // The dynamic-LDS ceiling is per-KERNEL state of the process, not of this handle: set it to the fixed upper bound every handle is
   // checked against (lds_limit), so that creating a second handle with smaller networks never lowers it under a live one's launches.
-  CREATE_CHK(hipFuncSetAttribute((const void*)k_ppo_grad<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_limit));
-  CREATE_CHK(hipFuncSetAttribute((const void*)k_ppo_act<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_limit));
-  CREATE_CHK(hipFuncSetAttribute((const void*)k_ppo_grad<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_limit));
-  CREATE_CHK(hipFuncSetAttribute((const void*)k_ppo_act<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_limit));
-  CREATE_CHK(hipDeviceSynchronize());
-  (void)hipSetDevice(cur);
-#undef CREATE_CHK
-  *out = h;
+  HIPCHK(hipFuncSetAttribute((const void*)k_ppo_grad<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_limit));
+  HIPCHK(hipFuncSetAttribute((const void*)k_ppo_act<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_limit));
+  HIPCHK(hipFuncSetAttribute((const void*)k_ppo_grad<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_limit));
+  HIPCHK(hipFuncSetAttribute((const void*)k_ppo_act<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_limit));
+  HIPCHK(hipDeviceSynchronize());
+  *out = h.release();
   return MM_OK;
 }
 
 // tools builds only (-DMM_PPO_PROF=1): buf = [workgroups][64] uint64 stage stamps of the next mm_ppo_grad launches; NULL switches it off
 extern "C" int mm_ppo_debug_set_prof(void* buf) {
-  PHIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_ppo_prof), &buf, sizeof(buf)));
+  HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_ppo_prof), &buf, sizeof(buf)));
   return MM_OK;
 }
 
@@ -656,9 +643,9 @@ extern "C" int mm_ppo_value_offset(const mm_ppo* h) { return h ? h->np_pi : 0; }
 
 extern "C" int mm_ppo_reset_optimizer(mm_ppo* h, void* stream) {
   if (!h) return pfail(MM_EARG, "mm_ppo_reset_optimizer: null handle");
-  PHIPCHK(hipMemsetAsync(h->m1, 0, sizeof(float) * h->np, (hipStream_t)stream));
-  PHIPCHK(hipMemsetAsync(h->m2, 0, sizeof(float) * h->np, (hipStream_t)stream));
-  PHIPCHK(hipMemsetAsync(h->step, 0, 2 * sizeof(float), (hipStream_t)stream));
+  HIPCHK(hipMemsetAsync(h->m1, 0, sizeof(float) * h->np, (hipStream_t)stream));
+  HIPCHK(hipMemsetAsync(h->m2, 0, sizeof(float) * h->np, (hipStream_t)stream));
+  HIPCHK(hipMemsetAsync(h->step, 0, 2 * sizeof(float), (hipStream_t)stream));
   return MM_OK;
 }
 
@@ -681,7 +668,7 @@ extern "C" int mm_ppo_act(mm_ppo* h, const float* params, const float* obs, cons
   const dim3 grid(action_out ? 2 * nb : nb), block(NTHREADS);
   if (rt == 2) hipLaunchKernelGGL(k_ppo_act<2>, grid, block, h->lds[1], (hipStream_t)stream, a);
   else hipLaunchKernelGGL(k_ppo_act<1>, grid, block, h->lds[0], (hipStream_t)stream, a);
-  PHIPCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return MM_OK;
 }
 
@@ -690,7 +677,7 @@ extern "C" int mm_ppo_store(const float* rwd, int rwd_cols, int rwd_col, float r
   if (!rwd || !ended || !reward_out || !trunc_out || !term_out || nenv <= 0 || rwd_col < 0 || rwd_col >= rwd_cols) return pfail(MM_EARG, "mm_ppo_store: bad argument");
   hipLaunchKernelGGL(k_ppo_store, dim3((nenv + 255) / 256), dim3(256), 0, (hipStream_t)stream, rwd, rwd_cols, rwd_col, reward_scale, ended,
                      truncated, nenv, reward_out, trunc_out, term_out);
-  PHIPCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return MM_OK;
 }
 
@@ -707,10 +694,10 @@ extern "C" int mm_ppo_grad(mm_ppo* h, const float* params, const float* obs, con
              h->cfg.clipping_epsilon, h->cfg.entropy_cost, h->cfg.value_cost};
   if (rt == 2) hipLaunchKernelGGL(k_ppo_grad<2>, dim3(2 * nb), dim3(NTHREADS), h->lds[1], (hipStream_t)stream, a);
   else hipLaunchKernelGGL(k_ppo_grad<1>, dim3(2 * nb), dim3(NTHREADS), h->lds[0], (hipStream_t)stream, a);
-  PHIPCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(k_ppo_reduce, dim3(h->nbq), dim3(NTHREADS), 0, (hipStream_t)stream, part_pi, nb, h->np_pi, part_vf, nb, h->np_vf, grad_out,
                      h->blocksq);
-  PHIPCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return MM_OK;
 }
 
@@ -725,11 +712,11 @@ extern "C" int mm_ppo_adam(mm_ppo* h, float* params, const float* grad, float gr
   DeviceGuard guard(h->device);
   if (recompute_norm) {
     hipLaunchKernelGGL(k_ppo_sumsq, dim3(h->nbq), dim3(RED_P), 0, (hipStream_t)stream, grad, h->np, h->blocksq);
-    PHIPCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
   }
   const mm_ppo_config& c = h->cfg;
   hipLaunchKernelGGL(k_ppo_adam, dim3((h->np + NTHREADS - 1) / NTHREADS), dim3(NTHREADS), 0, (hipStream_t)stream, params, grad, h->m1, h->m2, h->blocksq, h->nbq, h->step,
                      (unsigned*)(h->step + 1), h->np, grad_scale, c.learning_rate, c.beta1, c.beta2, c.adam_eps, c.max_grad_norm);
-  PHIPCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return MM_OK;
 }

@@ -94,6 +94,69 @@ FILE_FLAGS = {"myosim_inst_B.hip": ["-mllvm", "-sink-insts-to-avoid-spills=1", "
 #  workgroup's 131 k cycles; the gradient test against torch autograd holds its 2e-4 either way)
 
 
+MAX_BUILD_JOBS = 16
+
+
+def sched_for(base: str):
+    """-amdgpu-sched-strategy of an engine source file: the kernel instantiation units take one, the host files the compiler's"""
+    return SCHED_STRATEGY.get(base, SCHED_STRATEGY["default"]) if base.endswith(".hip") and "inst" in base else None
+
+
+def compile_command(src: str, out: str, extra=(), file_flags=None, sched_for=sched_for, device_only: str = "") -> list:
+    """THE hipcc command line of one translation unit (the library builds, and the tools/ that look at what the build compiles):
+    common flags, the file's own (file_flags: the library's table, FILE_FLAGS by default), `extra`, the file's scheduler strategy.
+    device_only: "-c" / "-S" compiles the device side alone into an unbundled object / assembly instead of the host object."""
+    base = os.path.basename(src)
+    sched = sched_for(base)
+    return (["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17"] + (["--cuda-device-only", "--no-gpu-bundle-output"] if device_only else ["-fPIC"]) +
+            EXTRA_FLAGS + (FILE_FLAGS if file_flags is None else file_flags).get(base, []) + list(extra) +
+            (["-mllvm", f"-amdgpu-sched-strategy={sched}"] if sched else []) + [device_only or "-c", "-o", out, src])
+
+
+def _build_library(lib_path: str, src_dir: str, headers, build_dir: str, file_flags, sched_for, own_headers=None,
+                   force: bool = False, verbose: bool = False, jobs: int = 0) -> str:
+    """One shared library from every *.hip of src_dir, compiled in parallel (at most MAX_BUILD_JOBS at a time) into build_dir and
+    linked.  A source is recompiled when it, one of `headers` or its own header (own_headers: {source file: header}) is newer than
+    its object; the compiler flags are part of the build's identity: a library built with other flags is rebuilt from scratch."""
+    import concurrent.futures
+    own_headers = own_headers or {}
+    srcs = sorted(os.path.join(src_dir, f) for f in os.listdir(src_dir) if f.endswith(".hip"))
+    stamp = os.path.join(build_dir, "flags.txt")
+    flags_now = " ".join(EXTRA_FLAGS) + " | " + repr(sorted(SCHED_STRATEGY.items())) + repr(sorted(file_flags.items()))
+    same_flags = os.path.exists(stamp) and open(stamp).read() == flags_now
+    force = force or (os.path.exists(lib_path) and os.path.isdir(build_dir) and not same_flags)
+    if not force and os.path.exists(lib_path) and (same_flags or not os.path.isdir(build_dir)) and \
+            all(os.path.getmtime(lib_path) >= os.path.getmtime(d) for d in srcs + list(headers) + list(own_headers.values())):
+        return lib_path
+    os.makedirs(build_dir, exist_ok=True)
+    newest_hdr = max(os.path.getmtime(h) for h in headers)
+
+    def compile_one(src):
+        obj = os.path.join(build_dir, os.path.basename(src)[:-4] + ".o")
+        own = own_headers.get(os.path.basename(src))
+        if not force and os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(src), newest_hdr, os.path.getmtime(own) if own else 0.0):
+            return obj
+        cmd = compile_command(src, obj, file_flags=file_flags, sched_for=sched_for)
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+        return obj
+    with concurrent.futures.ThreadPoolExecutor(max_workers=max(min(jobs or (os.cpu_count() or 1), len(srcs), MAX_BUILD_JOBS), 1)) as ex:
+        objs = list(ex.map(compile_one, srcs))
+    cmd = ["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib_path] + objs
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    with open(stamp, "w") as f:
+        f.write(flags_now)
+    return lib_path
+
+
+def _headers(*dirs, include=()):
+    return [os.path.join(d, f) for d in dirs for f in os.listdir(d) if f.endswith((".hpp", ".inc"))] + \
+           [os.path.join(_HERE, "..", "include", h) for h in include]
+
+
 def build(force: bool = False, verbose: bool = False, jobs: int = 0) -> str:
     """Compile the native libraries for gfx950 in-tree (hipcc cross-compiles without a GPU): the engine, libmyosim_hip.so, from
     the *.hip files directly under csrc/, then the inverse-dynamics library, libmyosim_inverse.so, from csrc/inverse/
@@ -107,45 +170,9 @@ def build(force: bool = False, verbose: bool = False, jobs: int = 0) -> str:
 def _build_engine(force: bool = False, verbose: bool = False, jobs: int = 0) -> str:
     """The engine library.  The kernel instantiations are spread over several translation units (myosim_inst_*.hip) that are
     compiled in parallel and linked into one .so."""
-    import concurrent.futures
-    srcs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip"))
-    hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hpp", ".inc"))] + \
-           [os.path.join(_HERE, "..", "include", h) for h in ("myosim.h", "myosim_model.h")]
-    ppo_hdr = os.path.join(_HERE, "..", "include", "myosim_ppo.h")         # seen by myosim_ppo.hip only
-    deps = srcs + hdrs + [ppo_hdr]
-    bdir = os.path.join(CSRC, "_build")
-    # the compiler flags are part of the build's identity: a library built with other flags is rebuilt from scratch
-    stamp, flags_now = os.path.join(bdir, "flags.txt"), " ".join(EXTRA_FLAGS) + " | " + repr(sorted(SCHED_STRATEGY.items())) + repr(sorted(FILE_FLAGS.items()))
-    same_flags = os.path.exists(stamp) and open(stamp).read() == flags_now
-    force = force or (os.path.exists(LIB_PATH) and os.path.isdir(bdir) and not same_flags)
-    if not force and os.path.exists(LIB_PATH) and (same_flags or not os.path.isdir(bdir)) and \
-            all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):
-        return LIB_PATH
-    os.makedirs(bdir, exist_ok=True)
-    newest_hdr = max(os.path.getmtime(h) for h in hdrs)
-
-    def compile_one(src):
-        obj = os.path.join(bdir, os.path.basename(src)[:-4] + ".o")
-        own_hdr = os.path.getmtime(ppo_hdr) if os.path.basename(src) == "myosim_ppo.hip" else 0.0
-        if not force and os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(src), newest_hdr, own_hdr):
-            return obj
-        sched = SCHED_STRATEGY.get(os.path.basename(src), SCHED_STRATEGY["default"])
-        cmd = (["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"] + EXTRA_FLAGS + FILE_FLAGS.get(os.path.basename(src), []) +
-               (["-mllvm", f"-amdgpu-sched-strategy={sched}"] if sched and src.endswith(".hip") and "inst" in os.path.basename(src) else []) +
-               ["-c", "-o", obj, src])
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.check_call(cmd)
-        return obj
-    with concurrent.futures.ThreadPoolExecutor(max_workers=jobs or min(len(srcs), os.cpu_count() or 1)) as ex:
-        objs = list(ex.map(compile_one, srcs))
-    cmd = ["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_PATH] + objs
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.check_call(cmd)
-    with open(stamp, "w") as f:
-        f.write(flags_now)
-    return LIB_PATH
+    return _build_library(LIB_PATH, CSRC, _headers(CSRC, include=("myosim.h", "myosim_model.h")), os.path.join(CSRC, "_build"), FILE_FLAGS,
+                          sched_for, own_headers={"myosim_ppo.hip": os.path.join(_HERE, "..", "include", "myosim_ppo.h")},   # seen by myosim_ppo.hip only
+                          force=force, verbose=verbose, jobs=jobs)
 
 
 MM_PPO_MAX_LAYERS, MM_PPO_MAX_WIDTH, MM_PPO_MAX_OBS, MM_PPO_MAX_OUT = 8, 128, 512, 256        # include/myosim_ppo.h

@@ -14,7 +14,6 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-import subprocess
 from typing import Dict, Optional, Sequence
 
 import numpy as np
@@ -26,7 +25,6 @@ CSRC = os.path.join(E.CSRC, "inverse")
 LIB_PATH = os.path.join(E.CSRC, "libmyosim_inverse.so")
 MM_INVERSE_ABI_VERSION = 1   # include/myosim_inverse.h
 (INFO_LANES, INFO_KERNEL_FAMILY, INFO_EFC_ROWS, INFO_NVP, INFO_NV, INFO_NU, INFO_NQ, INFO_LDS_PER_ENV, INFO_ARGS_SIZE) = range(9)
-MAX_BUILD_JOBS = 16
 # the general-row units take the flag the engine's general-row units take (engine.FILE_FLAGS)
 FILE_FLAGS = {"myosim_inverse_inst_D.hip": ["-mllvm", "-sink-insts-to-avoid-spills=1"],
               "myosim_inverse_inst_H.hip": ["-mllvm", "-sink-insts-to-avoid-spills=1"]}
@@ -50,42 +48,11 @@ class mm_inverse_args(C.Structure):
 
 
 def build(force: bool = False, verbose: bool = False, jobs: int = 0) -> str:
-    """Compile libmyosim_inverse.so for gfx950 in-tree (engine.build() calls this: one build step for both libraries).  Same
-    flags, flag stamp and mtime rule as the engine library; objects under csrc/_build/inverse/."""
-    import concurrent.futures
-    srcs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip"))
-    hdrs = [os.path.join(d, f) for d in (CSRC, E.CSRC) for f in os.listdir(d) if f.endswith((".hpp", ".inc"))] + \
-           [os.path.join(E._HERE, "..", "include", h) for h in ("myosim.h", "myosim_model.h", "myosim_inverse.h")]
-    bdir = os.path.join(E.CSRC, "_build", "inverse")
-    stamp, flags_now = os.path.join(bdir, "flags.txt"), " ".join(E.EXTRA_FLAGS) + " | " + repr(sorted(FILE_FLAGS.items()))
-    same_flags = os.path.exists(stamp) and open(stamp).read() == flags_now
-    force = force or (os.path.exists(LIB_PATH) and os.path.isdir(bdir) and not same_flags)
-    if not force and os.path.exists(LIB_PATH) and (same_flags or not os.path.isdir(bdir)) and \
-            all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in srcs + hdrs):
-        return LIB_PATH
-    os.makedirs(bdir, exist_ok=True)
-    newest_hdr = max(os.path.getmtime(h) for h in hdrs)
-
-    def compile_one(src):
-        obj = os.path.join(bdir, os.path.basename(src)[:-4] + ".o")
-        if not force and os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(src), newest_hdr):
-            return obj
-        cmd = (["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"] + E.EXTRA_FLAGS + FILE_FLAGS.get(os.path.basename(src), []) +
-               ["-mllvm", f"-amdgpu-sched-strategy={E.SCHED_STRATEGY['default']}", "-c", "-o", obj, src])
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.check_call(cmd)
-        return obj
-    workers = min(jobs or (os.cpu_count() or 1), len(srcs), MAX_BUILD_JOBS)
-    with concurrent.futures.ThreadPoolExecutor(max_workers=max(workers, 1)) as ex:
-        objs = list(ex.map(compile_one, srcs))
-    cmd = ["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_PATH] + objs
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.check_call(cmd)
-    with open(stamp, "w") as f:
-        f.write(flags_now)
-    return LIB_PATH
+    """Compile libmyosim_inverse.so for gfx950 in-tree (engine.build() calls this: one build step for both libraries).  The engine
+    library's build rule (engine._build_library); every unit takes the default scheduler strategy; objects under csrc/_build/inverse/."""
+    return E._build_library(LIB_PATH, CSRC, E._headers(CSRC, E.CSRC, include=("myosim.h", "myosim_model.h", "myosim_inverse.h")),
+                            os.path.join(E.CSRC, "_build", "inverse"), FILE_FLAGS, lambda base: E.SCHED_STRATEGY["default"],
+                            force=force, verbose=verbose, jobs=jobs)
 
 
 def lib():

@@ -3,7 +3,6 @@ bundles and their AMDGPU metadata notes read -- the instantiations the BASELINE 
 (a spilled VGPR in these 250-VGPR kernels is scratch traffic to HBM in the hot loops: round 3 took reorient from 74 to 0, the
 self-contact hand from 26 to 0, and the SGPR spills of the general-row kernels from 420...570 to below 260)."""
 import os
-import struct
 import sys
 import tempfile
 
@@ -13,30 +12,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 from myosuite_amd import engine as E
+from kernel_table import device_objects          # tools/kernel_table.py: the offload-bundle reader
 
 READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-
-
-def _device_objects(path):
-    d = open(path, "rb").read()
-    magic = b"__CLANG_OFFLOAD_BUNDLE__"
-    i = d.find(magic)
-    while i >= 0:
-        p = i + len(magic)
-        (n,) = struct.unpack_from("<Q", d, p); p += 8
-        for _ in range(n):
-            off, size, tl = struct.unpack_from("<QQQ", d, p); p += 24
-            triple = d[p:p + tl].decode(); p += tl
-            if "gfx950" in triple and size:
-                yield d[i + off:i + off + size]
-        i = d.find(magic, i + len(magic))
 
 
 def _kernel_table():
     import isa_stats
     tab = {}
     with tempfile.TemporaryDirectory() as tmp:
-        for k, blob in enumerate(_device_objects(E.LIB_PATH)):
+        for k, blob in enumerate(device_objects(E.LIB_PATH)):
             f = os.path.join(tmp, f"{k}.co")
             open(f, "wb").write(blob)
             for rec in isa_stats.notes(f):

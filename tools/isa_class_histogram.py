@@ -119,14 +119,10 @@ def stage_of(fn):
 
 def assembly(unit):
     src = os.path.join(E.CSRC, f"myosim_{unit}.hip")
-    base = os.path.basename(src)
-    sched = E.SCHED_STRATEGY.get(base, E.SCHED_STRATEGY["default"])
     out = os.path.join(tempfile.gettempdir(), f"isa_hist_{unit}.s")
     deps = [src] + [os.path.join(E.CSRC, f) for f in os.listdir(E.CSRC) if f.endswith((".hpp", ".inc"))]
     if not (os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(d) for d in deps)):
-        cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "--no-gpu-bundle-output", "-gline-tables-only"] + \
-              E.EXTRA_FLAGS + E.FILE_FLAGS.get(base, []) + ["-mllvm", f"-amdgpu-sched-strategy={sched}", "-S", "-o", out, src]
-        subprocess.check_call(cmd, stderr=subprocess.DEVNULL)
+        subprocess.check_call(E.compile_command(src, out, extra=["-gline-tables-only"], device_only="-S"), stderr=subprocess.DEVNULL)
     return open(out).read().split("\n")
 
 

@@ -29,12 +29,8 @@ HDR = os.path.join(E.CSRC, "myosim_engine_kernel.hpp")
 
 def assembly(unit):
     src = os.path.join(E.CSRC, f"myosim_{unit}.hip")
-    base = os.path.basename(src)
-    sched = E.SCHED_STRATEGY.get(base, E.SCHED_STRATEGY["default"])
     out = os.path.join(tempfile.mkdtemp(prefix="isa_"), unit + ".s")
-    cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "--no-gpu-bundle-output", "-gline-tables-only"] + \
-          E.EXTRA_FLAGS + E.FILE_FLAGS.get(base, []) + ["-mllvm", f"-amdgpu-sched-strategy={sched}", "-S", "-o", out, src]
-    subprocess.check_call(cmd, stderr=subprocess.DEVNULL)
+    subprocess.check_call(E.compile_command(src, out, extra=["-gline-tables-only"], device_only="-S"), stderr=subprocess.DEVNULL)
     return open(out).read().split("\n")
 
 
