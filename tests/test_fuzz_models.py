@@ -152,7 +152,8 @@ def test_gpu_random_models_match_the_oracle(oracle_lib, seed):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("seed,integrator", [(s_, i_) for s_ in (1, 4, 6, 13, 21) for i_ in (1, 3)], ids=lambda v: str(v))
+# (seed 11 on RK4: a 4-dof general-row model, the only case of the suite on k_engine<16, 4, general rows, RK4> -- tests/test_wide_models.py)
+@pytest.mark.parametrize("seed,integrator", [(s_, i_) for s_ in (1, 4, 6, 13, 21) for i_ in (1, 3)] + [(11, 1)], ids=lambda v: str(v))
 def test_gpu_random_models_on_rk4_and_implicitfast(oracle_lib, seed, integrator):
     """the same generated models on the other two integrators (RK4 = 1, implicitfast = 3): kernels exist for the elbow- / hand- /
     leg-sized widths; a model whose width has no kernel of that integrator must be REFUSED (MM_EUNSUPPORTED), never stepped by

@@ -16,12 +16,14 @@ Error measure: max |gpu - ref| over the env, divided by the largest max-abs of t
 that env (the cancellation-free scale).  Bounds: the forward-stage bounds of tests/test_gpu_widths.py CONFIGS -- 2e-4 for the
 limit-rows-only family, 5e-4 for the general-row family.
 
-Instantiations no synth model reaches (they are built, and listed in test_library_holds_the_seventeen_kernels, but not run here):
-<32,32,0>, <64,32,0>, <64,40,0> (limit-rows-only models with more than 24 dofs) and <64,40,1> (general rows, 37-40 dofs).
+The instantiations of the 32 and 40 tiles that no synth model reaches -- <32,32,0>, <64,32,0>, <64,40,0> and <64,40,1> -- run on the
+forests of tests/test_wide_models.py (W28 at 32 and 64 lanes, W40, G38): GPU_MODELS reaches all seventeen kernels, which
+test_wide_models.py::test_every_compiled_kernel_has_a_parity_case asserts on the CPU.
 
 Measured on an MI355X (worst value of the measure over the 65 states; MEASURED_WORST holds the per-model figures):
 
-    constraints off, all twenty (model, width) cases: every term <= 2.5e-6 (worst: tree_chain-G32 qfrc_inverse 2.46e-6, hand bias 2.0e-6)
+    the forests W28 / W40 / G38:                        qfrc_inverse <= 3.3e-6 (limit rows), 9.2e-5 on G38 (its constraint term)
+    constraints off, the twenty synth (model, width) cases: every term <= 2.5e-6 (worst: tree_chain-G32 qfrc_inverse 2.46e-6, hand bias 2.0e-6)
     constraints on / round trip, mass, bias, passive:  <= 6.2e-6 everywhere
     constraints on / round trip, constraint term:      <= 4.2e-6, except tendon_limit_toy 3.3e-4 and hand_reorient 3.4e-4 (inside 5e-4)
     actuator outputs (hand / leg / motorfinger):       moment 1.7e-5, gain 3.6e-6, bias 2.3e-6, length 2.0e-6, velocity 9.3e-6 (hand, the worst)
@@ -64,14 +66,15 @@ NOISE = 0.5          # family (b): qacc = forward solution + NOISE * max|forward
 CON_LIMIT_JOINT, CON_LIMIT_TENDON, CON_CONTACT, CON_EQUALITY, CON_FRICTION = (S.C["MM_CON_LIMIT_JOINT"], S.C["MM_CON_LIMIT_TENDON"],
                                                                               S.C["MM_CON_CONTACT"], S.C["MM_CON_EQUALITY"], S.C["MM_CON_FRICTION_DOF"])
 
-# (model, lanes per env, bound): together every k_inverse instantiation a synth model can reach.  (plane_toy is left out: all its
+# (model, lanes per env, bound): together every k_inverse instantiation -- the last four on tests/test_wide_models.py's forests.  (plane_toy is left out: all its
 # joints are free, so every state is qpos0, where its boxes rest exactly at the contact margin -- every state is marginal; its
 # instantiation, <64,32,1>, is hand_reorient's.)
 GPU_MODELS = [("elbow", 4, TOL_LIMIT), ("elbow", 8, TOL_LIMIT), ("elbow", 16, TOL_LIMIT), ("elbow", 32, TOL_LIMIT), ("elbow", 64, TOL_LIMIT),
               ("finger", 8, TOL_LIMIT), ("hand", 32, TOL_LIMIT), ("hand", 64, TOL_LIMIT), ("tree_star", 32, TOL_LIMIT),
               ("friction_toy", 16, TOL_GEN), ("tendon_limit_toy", 16, TOL_GEN), ("contact_toy", 32, TOL_GEN), ("tree_chain", 32, TOL_GEN),
               ("hand_hold", 32, TOL_GEN), ("hand_reorient", 64, TOL_GEN), ("leg", 64, TOL_GEN),
-              ("hand_contact", 64, TOL_GEN), ("hand_keyturn", 64, TOL_GEN), ("torso", 64, TOL_GEN)]
+              ("hand_contact", 64, TOL_GEN), ("hand_keyturn", 64, TOL_GEN), ("torso", 64, TOL_GEN),
+              ("W28", 32, TOL_LIMIT), ("W28", 64, TOL_LIMIT), ("W40", 64, TOL_LIMIT), ("G38", 64, TOL_GEN)]
 # Inputs changed to keep the marginal share under its cap.  With the object at qpos0, hand_hold's uniform-over-the-range finger poses
 # put a finger through the MIDDLE of the held ellipsoid in 6 of 65 states (oracle con_dist -1.8 ... -3.2 cm against semi-axes of 2.5 /
 # 3.6 / 3 cm): there the nearest surface point is not unique and the fp64 oracle's own contact normal turns by 50 - 100 degrees under a
@@ -95,19 +98,31 @@ TERMS = ("qfrc_inverse", "qfrc_mass", "qfrc_bias", "qfrc_passive", "qfrc_constra
 MEASURED_WORST = {   # qfrc_inverse, n = 65
     "off": {"elbow": 2.3e-7, "finger": 4.6e-7, "hand": 1.8e-6, "tree_star": 8.4e-7, "friction_toy": 2.8e-7, "tendon_limit_toy": 2.3e-7,
             "contact_toy": 1.3e-7, "tree_chain": 2.5e-6, "hand_hold": 1.6e-7, "hand_reorient": 1.2e-7, "leg": 3.3e-7, "hand_contact": 1.8e-6,
-            "hand_keyturn": 1.8e-6, "torso": 5.4e-7},
+            "hand_keyturn": 1.8e-6, "torso": 5.4e-7,
+            "W28": 8.0e-7, "W40": 1.2e-6, "G38": 7.7e-7},
     "on-a": {"elbow": 7.6e-7, "finger": 3.0e-7, "hand": 1.0e-6, "tree_star": 2.5e-6, "friction_toy": 1.6e-6, "tendon_limit_toy": 3.3e-4,
              "contact_toy": 4.1e-6, "tree_chain": 6.2e-6, "hand_hold": 12.9, "hand_reorient": 1.5e-2, "leg": 1.3e-6, "hand_contact": 1.8e-6,
-             "hand_keyturn": 4.2e-6, "torso": 1.2e-6},
+             "hand_keyturn": 4.2e-6, "torso": 1.2e-6,
+             "W28": 1.9e-6, "W40": 3.1e-6, "G38": 9.2e-5},
     "on-b": {"elbow": 2.8e-7, "finger": 3.1e-7, "hand": 8.7e-7, "tree_star": 8.1e-7, "friction_toy": 5.4e-7, "tendon_limit_toy": 2.7e-4,
              "contact_toy": 3.4e-7, "tree_chain": 2.0e-6, "hand_hold": 1.14, "hand_reorient": 3.4e-4, "leg": 3.4e-7, "hand_contact": 2.6e-6,
-             "hand_keyturn": 2.5e-6, "torso": 5.2e-7},
+             "hand_keyturn": 2.5e-6, "torso": 5.2e-7,
+             "W28": 1.0e-6, "W40": 1.2e-6, "G38": 1.2e-6},
     "trip": {"elbow": 7.4e-7, "finger": 3.1e-7, "hand": 1.1e-6, "tree_star": 2.4e-6, "friction_toy": 1.7e-6, "tendon_limit_toy": 3.3e-4,
              "contact_toy": 4.1e-6, "tree_chain": 5.5e-6, "hand_hold": 1.3, "hand_reorient": 1.5e-2, "leg": 1.3e-6, "hand_contact": 1.8e-6,
-             "hand_keyturn": 4.0e-6, "torso": 9.3e-7}}
+             "hand_keyturn": 4.0e-6, "torso": 9.3e-7,
+             "W28": 1.8e-6, "W40": 3.3e-6, "G38": 8.7e-5}}
 
 
 # ------------------------------------------------------------------ inputs and the fp64 reference
+def get_model(name):
+    """a synth model by name, or one of the forests of tests/test_wide_models.py (not in synth.builders(): test models only)"""
+    if name in synth.builders():
+        return synth.get_model(name)
+    from test_wide_models import wide_model          # (same directory; imported here: that module imports this one)
+    return wide_model(name)
+
+
 def make_states(cm, n=NSTATE, seed=SEED, lift=0.0):
     rng = np.random.default_rng(seed)
     q = np.tile(cm.qpos0.astype(np.float64), (n, 1))
@@ -180,7 +195,7 @@ def scale_of(t):
 def refs(name):
     """(compiled model, states, [Ref per state]) -- computed once per model and shared by every test; never modified"""
     O.build()
-    cm = synth.get_model(name)
+    cm = get_model(name)
     om = O.OracleModel(cm)
     st = make_states(cm, lift=LIFTED.get(name, 0.0))
     out = []
@@ -343,12 +358,12 @@ def test_trajectory_finite_differences():
 # ------------------------------------------------------------------ GPU
 @functools.lru_cache(maxsize=None)
 def inv_model(name, lanes):
-    return INV.InverseModel(synth.get_model(name), lanes_per_env=lanes)
+    return INV.InverseModel(get_model(name), lanes_per_env=lanes)
 
 
 @functools.lru_cache(maxsize=None)
 def hip_model(name, lanes):
-    return E.HipModel(synth.get_model(name), lanes_per_env=lanes)
+    return E.HipModel(get_model(name), lanes_per_env=lanes)
 
 
 def batch_state(hm, st, n):
